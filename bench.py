@@ -24,7 +24,26 @@ collective on the data path; barrier + max-over-ranks timing; value = all
 ranks' bytes / max time ("weak").  RCCL ("nccl") carries the barrier, the
 timing reductions and the config-5 scatter/gather leg.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set up, warm up, time
+the K steps (each kernel's HIP events come from its own dispatch inside those
+steps and feed the roofline fields at no extra run), write the outputs of the
+last timed step if `--dump-outputs DIR` is given, print the line.  Everything
+else the benchmark measures or checks runs only with `--full`: the on-device
+verification of what was timed (`verified`), the CPU baseline, the
+host-in/host-out leg, and at N > 1 (or --dist-world1 / --multi-devices) the
+scatter/gather and multi_device legs; the --no-* options choose among them.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+the C ABI receives it: the parity buffer its encode wrote and the data buffer
+its decode rebuilt in place.  Per buffer: a fixed, seeded sample of its bytes
+as float32 (`parity_sample.npy`; `decoded_lost_sample.npy` is drawn from the
+rebuilt blocks only) and the byte sum of every block as float64
+(`parity_block_sums.npy`, `decoded_block_sums.npy`; a seeded choice of 2^20
+blocks where a buffer has more), under 64 MB in all; at
+N > 1 each rank writes its own files, `<name>_rank<r>.npy`.  The inputs are a
+seeded device fill, identical from run to run.
 
 `--rehearse-cpu --dist-backend gloo` swaps the device calls for CPU stand-ins
 (tools/cpu_rehearsal.py) to exercise the launcher and the N>1 bookkeeping
@@ -63,6 +82,13 @@ def parse():
     ap.add_argument("--workload", default="cfg3",
                     help=f"one of {sorted(WORKLOADS)}, or a custom shape k,m,bs,S")
     ap.add_argument("--stripes", type=int, default=0, help="override stripes per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: verification of what was "
+                         "timed, the CPU baseline, the host-in/host-out leg, the scatter and "
+                         "multi_device legs (the --no-* options choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (parity written by its "
+                         "encode, data rebuilt by its decode) as DIR/<name>.npy (module doc)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline wall budget")
     ap.add_argument("--no-verify", action="store_true")
@@ -147,6 +173,39 @@ def erasure_pattern(np, S, k, m, lost=1, start=0):
     for q in range(lost):
         bm[np.arange(S), (c + q) % m + m * ((7 * c + q) % (k // m))] = 0
     return bm
+
+
+DUMP_SAMPLE = 1 << 21  # sampled bytes per buffer (float32: 8 MiB a file)
+DUMP_SUMS = 1 << 20    # block sums per buffer (float64: 8 MiB a file)
+
+
+def dump_outputs(torch, np, out_dir, suffix, parity, data, bm, S, k, m, bs):
+    """--dump-outputs: the two buffers the last timed step wrote, as its caller
+    holds them after the step -- `parity` (S*m blocks, written by the encode)
+    and `data` (S*k blocks, its lost blocks per `bm` rebuilt in place by the
+    decode) -- as four .npy files (module doc).  Every choice of bytes and
+    blocks is drawn from SEED, so two runs with the same arguments write the
+    same positions; a buffer no larger than the sample is written whole."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    rng = np.random.default_rng(SEED)
+
+    def pick(t, limit):  # t[sorted seeded choice of `limit` rows], or all of t
+        if t.shape[0] <= limit:
+            return t
+        idx = np.sort(rng.integers(0, t.shape[0], limit))
+        return t[torch.from_numpy(idx).to(t.device)]
+
+    lost = torch.from_numpy(np.ascontiguousarray(bm[:, :k] == 0)).to(data.device)
+    files = {
+        "parity_sample": pick(parity.reshape(-1), DUMP_SAMPLE).to(torch.float32),
+        "parity_block_sums": pick(parity.view(S * m, bs).sum(1, dtype=torch.float64), DUMP_SUMS),
+        "decoded_lost_sample": pick(data.view(S, k, bs)[lost].reshape(-1),
+                                    DUMP_SAMPLE).to(torch.float32),
+        "decoded_block_sums": pick(data.view(S * k, bs).sum(1, dtype=torch.float64), DUMP_SUMS),
+    }
+    for name, t in files.items():
+        np.save(out_dir / f"{name}{suffix}.npy", t.cpu().numpy())
 
 
 def load_traffic(workload):
@@ -864,6 +923,8 @@ def main():
         print(json.dumps(cpu_measure(json.loads(sys.argv[2]))), flush=True)
         return
     args = parse()
+    if args.multi_devices.strip().lower() not in ("", "none") and not args.full:
+        sys.exit("--multi-devices names a leg that runs only with --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.rank_grace))
     run_rank(args)
@@ -1036,6 +1097,11 @@ def run_rank(args):
     enc_ms = sum(enc_list) / args.steps
     dec_ms = sum(dec_list) / args.steps
 
+    if args.dump_outputs:  # what the last timed step's encode and decode wrote
+        last = args.warmup + args.steps - 1
+        dump_outputs(torch, np, args.dump_outputs, f"_rank{rank}" if world > 1 else "",
+                     sets[last % NSETS][1], sets[(last + NSETS - 1) % NSETS][0], bm, S, k, m, bs)
+
     # ---- optional: the same steps replayed from one captured hipGraph ----------
     # (xec_decode_device has no host work, so a whole rotation of NSETS steps --
     # 2*NSETS kernels plus the decode's status memsets and check kernels -- is
@@ -1066,11 +1132,11 @@ def run_rank(args):
                  "note": "one captured rotation of steps replayed; rank-local wall clock"}
         del g
 
-    # ---- correctness of what was timed -------------------------------------
+    # ---- correctness of what was timed (--full) ----------------------------
     # parity == XOR of each class's data (encode), then erase -> decode ->
     # data == a fresh device fill (decode); all on the device, no oracle.
     ok = True
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         fresh = torch.empty_like(sets[0][0])
         for i, (d, p, seed_base) in enumerate(sets):
             blocks = d.view(S, k // m, m, bs).view(torch.int64)
@@ -1137,7 +1203,8 @@ def run_rank(args):
         dominant = ("decode" if rl["decode"]["avg_launch_ms"] >= rl["encode"]["avg_launch_ms"]
                     else "encode")
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.lost == 1 and not args.rehearse_cpu:
+        if (args.full and world == 1 and not args.no_cpu_baseline and args.lost == 1
+                and not args.rehearse_cpu):
             numa = gpu_numa_node(torch, dev) if devname == "cuda" else {}
             cpu = cpu_baseline(args.workload, k, m, bs, S_per, args.cpu_seconds,
                                numa.get("numa_node"))
@@ -1180,7 +1247,7 @@ def run_rank(args):
             "decode_GBps_per_gpu": round(b_dec / (dec_ms_max * 1e-3) / 1e9, 1),
             "data_GBps_reference_convention": round(
                 2 * args.steps * stripes_done * k * bs / elapsed / 1e9, 2),
-            "verified": bad == 0.0,
+            "verified": bad == 0.0 if args.full else None,  # a plain run checks nothing
             "graph": graph,
             "dist": {"backend": dist.get_backend() if use_dist else None,
                      "ranks_seen": dist.get_world_size() if use_dist else 1,
@@ -1228,8 +1295,9 @@ def run_rank(args):
     #  * host_pipeline: the north star's host-in / host-out rate, every rank;
     #  * scatter: config 5's RCCL scatter / gather (N > 1; gloo cannot carry
     #    HIP buffers, so with --dist-backend gloo on a GPU it is skipped).
-    host_leg = not args.no_host_pipeline and not args.rehearse_cpu and args.lost == 1 and not bad
-    scatter_leg = (use_dist and not args.no_scatter and not bad
+    host_leg = (args.full and not args.no_host_pipeline and not args.rehearse_cpu
+                and args.lost == 1 and not bad)
+    scatter_leg = (args.full and use_dist and not args.no_scatter and not bad
                    and (backend == "nccl" or args.rehearse_cpu))
     if host_leg or scatter_leg:
         import threading
@@ -1332,7 +1400,7 @@ def run_rank(args):
     # their buffers and met; meanwhile the other ranks wait on the host
     # (host_side_wait), so no rank's collective kernel spins on a GPU the child
     # is timing.
-    multi = None if bad else multi_device_list(args, world, ndev)
+    multi = multi_device_list(args, world, ndev) if args.full and not bad else None
     if multi is not None:
         del sets, scratch, d_bm, d_status, events
         if devname == "cuda":

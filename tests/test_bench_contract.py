@@ -17,9 +17,12 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
             "roofline", "cpu_baseline"}
 
 
-def run_bench(*args):
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True,
-                       text=True, timeout=600, cwd=ROOT)
+def run_bench(*args, full=True):
+    """One bench.py run; with --full unless told otherwise, since what these
+    tests check beside the headline (verified, cpu_baseline, the legs) is
+    measured only there."""
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), *(["--full"] if full else []),
+                        *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     # stdout carries exactly the result line (RCCL's init banner and any other
     # library output go to stderr: bench.py _result_stream)
@@ -136,3 +139,46 @@ def test_bench_default_roofline_recomputes_from_profile():
     frac = r["algorithmic_bytes_per_launch"] / float(row["AverageNs"]) / 8000.0
     assert round(frac, 3) == round(rp["frac"], 3)
     assert 0.85 < rp["over_hip_events_ms"] < 1.15, r
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """A plain run (no --full) measures the headline only -- nothing verified,
+    no CPU baseline, no leg -- and --dump-outputs writes what its last timed
+    step computed.  With --steps 3 --warmup 1 the last step is step 3: it
+    encodes buffer set 0 and decodes set 2 (seeds 1896 and 1896 + 2 * 2**40),
+    so the files must equal what dump_outputs makes of the CPU oracle's
+    batches of those seeds, bit for bit (the bytes are small integers, exact in
+    float32; a block's byte sum is exact in float64)."""
+    import numpy as np
+    import torch
+
+    import bench
+    out = run_bench("--workload", "cfg2", "--stripes", "64", "--steps", "3", "--warmup", "1",
+                    "--dump-outputs", str(tmp_path / "got"), full=False)
+    assert REQUIRED <= set(out)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    # value = the timed steps' algorithmic bytes / their time, to the line's
+    # rounding (ms_per_step to 4 decimals, value to 2)
+    rounding = 0.5e-4 / out["ms_per_step"] + 0.5e-2 / out["value"]
+    timed_bytes = out["ms_per_step"] * 3e-3 * out["value"] * 1e9
+    assert abs(timed_bytes / (3 * 2 * 64 * 9 * 65536) - 1) <= rounding + rounding ** 2
+    assert out["verified"] is None and out["cpu_baseline"] is None
+    assert not {"host_pipeline", "scatter", "multi_device"} & set(out)
+    assert out["roofline"]["avg_launch_ms"] > 0  # from the timed steps' own events
+
+    S, k, m, bs = 64, 8, 1, 65536
+    _, ref_p = oracle.batch(S, k, m, bs, bench.SEED)
+    ref_d, _ = oracle.batch(S, k, m, bs, bench.SEED + 2 * (1 << 40))
+    bm = bench.erasure_pattern(np, S, k, m)
+    bench.dump_outputs(torch, np, tmp_path / "want", "", torch.from_numpy(ref_p),
+                       torch.from_numpy(ref_d), bm, S, k, m, bs)
+    names = {"parity_sample": np.float32, "parity_block_sums": np.float64,
+             "decoded_lost_sample": np.float32, "decoded_block_sums": np.float64}
+    assert sorted(f.name for f in (tmp_path / "got").iterdir()) == sorted(n + ".npy" for n in names)
+    for name, dtype in names.items():
+        got = np.load(tmp_path / "got" / f"{name}.npy")
+        want = np.load(tmp_path / "want" / f"{name}.npy")
+        assert got.dtype == dtype and got.shape == want.shape and got.size > 0
+        assert np.array_equal(got, want), name
+    # both buffers here are larger than the sample: the seeded choice was taken
+    assert np.load(tmp_path / "got" / "parity_sample.npy").size == bench.DUMP_SAMPLE

@@ -18,9 +18,10 @@ import pytest
 from conftest import ROOT
 
 
-def _bench(*args, timeout=300):
-    return subprocess.run([sys.executable, str(ROOT / "bench.py"), *args], capture_output=True,
-                          text=True, timeout=timeout, cwd=ROOT)
+def _bench(*args, timeout=300, full=True):
+    """With --full unless told otherwise: verification and the legs run only there."""
+    return subprocess.run([sys.executable, str(ROOT / "bench.py"), *(["--full"] if full else []),
+                           *args], capture_output=True, text=True, timeout=timeout, cwd=ROOT)
 
 
 @pytest.mark.parametrize("n", [2, 4, 8])  # 8: the driver's largest scaling run
@@ -56,6 +57,92 @@ def test_launcher_plain_command(n):
     assert "error" not in md
 
 
+def test_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full, at N=2: the line still carries the headline keys, but
+    nothing is verified and no leg runs; --dump-outputs writes each rank's
+    last-step outputs (`<name>_rank<r>.npy`), equal to what dump_outputs makes
+    of that rank's stripes computed here.  --steps 2 --warmup 1: the last step
+    is step 2, which encodes buffer set 2 and decodes set 1."""
+    import numpy as np
+    import torch
+
+    import bench
+    sys.path.insert(0, str(ROOT / "tools"))
+    from cpu_rehearsal import CpuXec
+    p = _bench("--gpus", "2", "--rehearse-cpu", "--dist-backend", "gloo", "--workload",
+               "8,2,4096,5", "--steps", "2", "--warmup", "1", "--dump-outputs",
+               str(tmp_path / "got"), full=False)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), p.stdout
+    out = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert out["verified"] is None and out["cpu_baseline"] is None
+    assert not {"host_pipeline", "scatter", "multi_device"} & set(out)
+    S, k, m, bs = 5, 8, 2, 4096
+    x = CpuXec()
+    names = ["parity_sample", "parity_block_sums", "decoded_lost_sample", "decoded_block_sums"]
+    assert sorted(f.name for f in (tmp_path / "got").iterdir()) == sorted(
+        f"{n}_rank{r}.npy" for n in names for r in range(2))
+    for r in range(2):
+        start = r * S
+        bufs = {}
+        for s in (1, 2):  # the sets step 2 decodes and encodes
+            d = torch.empty(S * k * bs, dtype=torch.uint8)
+            par = torch.empty(S * m * bs, dtype=torch.uint8)
+            x.fill_splitmix64(d, S, k * bs, bench.SEED + start + s * (1 << 40))
+            x.encode(d, par, S, bs, k, m)
+            bufs[s] = (d, par)
+        bm = bench.erasure_pattern(np, S, k, m, 1, start)
+        bench.dump_outputs(torch, np, tmp_path / "want", f"_rank{r}", bufs[2][1], bufs[1][0], bm,
+                           S, k, m, bs)
+        for n in names:
+            got = np.load(tmp_path / "got" / f"{n}_rank{r}.npy")
+            want = np.load(tmp_path / "want" / f"{n}_rank{r}.npy")
+            assert got.dtype == want.dtype and got.dtype in (np.float32, np.float64)
+            assert np.array_equal(got, want), (n, r)
+        # small buffers are written whole: one lost block per stripe, every parity byte
+        assert np.load(tmp_path / "got" / f"decoded_lost_sample_rank{r}.npy").size == S * bs
+        assert np.load(tmp_path / "got" / f"parity_block_sums_rank{r}.npy").size == S * m
+
+
+def test_dump_outputs_samples_large_buffers_by_seed(tmp_path):
+    """Above DUMP_SAMPLE bytes / DUMP_SUMS blocks the files hold a seeded choice:
+    the same positions on every call, values taken from the buffer."""
+    import numpy as np
+    import torch
+
+    import bench
+    S, k, m, bs = (bench.DUMP_SUMS >> 2) + 3, 8, 1, 8  # S*k blocks > DUMP_SUMS, S*m*bs > DUMP_SAMPLE
+    g = torch.Generator().manual_seed(5)
+    data = torch.randint(0, 256, (S * k * bs,), dtype=torch.uint8, generator=g)
+    parity = torch.randint(0, 256, (S * m * bs,), dtype=torch.uint8, generator=g)
+    bm = bench.erasure_pattern(np, S, k, m)
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, np, tmp_path / d, "", parity, data, bm, S, k, m, bs)
+    total = 0
+    for f in sorted((tmp_path / "a").iterdir()):
+        a, b = np.load(f), np.load(tmp_path / "b" / f.name)
+        assert np.array_equal(a, b), f.name
+        total += a.nbytes
+    assert total <= 64e6
+    ps = np.load(tmp_path / "a" / "parity_sample.npy")
+    assert ps.size == bench.DUMP_SAMPLE and ps.dtype == np.float32
+    idx = np.sort(np.random.default_rng(bench.SEED).integers(0, parity.numel(), bench.DUMP_SAMPLE))
+    assert np.array_equal(ps, parity.numpy()[idx].astype(np.float32))  # the first seeded draw
+    sums = np.load(tmp_path / "a" / "decoded_block_sums.npy")
+    assert sums.size == bench.DUMP_SUMS and sums.dtype == np.float64
+    assert set(sums.tolist()) <= set(data.view(S * k, bs).sum(1, dtype=torch.float64).tolist())
+
+
+def test_multi_devices_list_needs_full():
+    p = _bench("--rehearse-cpu", "--dist-backend", "gloo", "--workload", "4,1,4096,3",
+               "--steps", "2", "--warmup", "1", "--multi-devices", "0,0", full=False)
+    assert p.returncode != 0 and "--full" in p.stderr
+    assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
 def test_torchrun_launch_one_line():
     """Launched the way the driver launches N > 1 (torch.distributed.run, one rank
     per process, WORLD_SIZE set): still exactly one line on stdout."""
@@ -65,7 +152,7 @@ def test_torchrun_launch_one_line():
         port = s.getsockname()[1]
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "4", "--master-addr", "127.0.0.1", "--master-port",
-                        str(port), str(ROOT / "bench.py"), "--gpus", "4", "--rehearse-cpu",
+                        str(port), str(ROOT / "bench.py"), "--full", "--gpus", "4", "--rehearse-cpu",
                         "--dist-backend", "gloo", "--workload", "8,2,4096,5", "--steps", "2",
                         "--warmup", "1"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -153,9 +240,9 @@ def test_topology_record_in_the_line(stub, path):
     the CPU has no runtime to ask."""
     import os
     env = dict(os.environ, XEC_TOPOLOGY_STUB=stub)
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4", "--rehearse-cpu",
-                        "--dist-backend", "gloo", "--workload", "8,2,4096,5", "--steps", "2",
-                        "--warmup", "1", "--multi-devices", "none"],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "4",
+                        "--rehearse-cpu", "--dist-backend", "gloo", "--workload", "8,2,4096,5",
+                        "--steps", "2", "--warmup", "1", "--multi-devices", "none"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])
@@ -170,9 +257,9 @@ def test_topology_record_in_the_line(stub, path):
 def test_topology_record_needs_a_runtime_or_a_stub():
     import os
     env = {k: v for k, v in os.environ.items() if k != "XEC_TOPOLOGY_STUB"}
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--rehearse-cpu",
-                        "--dist-backend", "gloo", "--workload", "8,2,4096,5", "--steps", "2",
-                        "--warmup", "1", "--multi-devices", "none"],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2",
+                        "--rehearse-cpu", "--dist-backend", "gloo", "--workload", "8,2,4096,5",
+                        "--steps", "2", "--warmup", "1", "--multi-devices", "none"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     out = json.loads(p.stdout.strip().splitlines()[-1])

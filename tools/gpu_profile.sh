@@ -18,7 +18,7 @@ cd "$R"
 python3 -c "import sys; sys.path.insert(0, 'erasure-code-benchmark_amd'); import xec; print(xec.build_info())" \
   > "$OUT/build_info.txt"
 timeout -k 10 300 rocprofv3 --marker-trace --kernel-trace --stats -d "$OUT/trace" -o kt --output-format csv \
-  -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/bench_trace.log" 2>&1
+  -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/bench_trace.log" 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace -d "$OUT/pmc_$C" -o pmc --output-format csv \
     -- python3 bench.py --no-cpu-baseline --no-host-pipeline --no-verify --steps 5 --warmup 2 "$@" > "$OUT/bench_$C.log" 2>&1

@@ -15,5 +15,5 @@ timeout -k 10 300 python -u tools/fuzz_harness.py --cases 40 --seed $((s + 3)) -
 tail -1 $o/fuzz_harness.log
 timeout -k 10 200 python -u tools/soak.py --seconds 120 --out $o/soak.json > $o/soak.log 2>&1 || { tail $o/soak.log; exit 1; }
 tail -1 $o/soak.log
-timeout -k 10 300 python -u bench.py --no-cpu-baseline > $o/bench.log 2>&1 || { tail $o/bench.log; exit 1; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $o/bench.log 2>&1 || { tail $o/bench.log; exit 1; }
 grep -o '"value": [0-9.]*' $o/bench.log
