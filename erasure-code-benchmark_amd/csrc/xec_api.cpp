@@ -38,6 +38,7 @@ thread_local int g_decode_tiling = 0;  // 0 auto, 1 stripe, 2 class, 3 list, 4 m
 thread_local int g_arg_cap_used = 0;   // xec_decode_arg_capacity_used
 thread_local int g_tiling_used = 0;    // xec_decode_tiling_used: this thread's last xec_decode
 thread_local int g_rotation = 0;       // xec_set_rotation: 0 automatic, -1 none, > 0 tiles
+thread_local int g_repair_tiling_used = 0;  // xec_repair_tiling_used: this thread's last repair
 
 constexpr size_t kBlockMultiple = 256;  // XOREC_BLOCK_SIZE_MULTIPLE
 constexpr size_t kMinBlock = 256;       // XOREC_MIN_BLOCK_SIZE
@@ -1060,6 +1061,136 @@ xec_status xec_decode_device_list(void* d_data, const void* d_parity, size_t S, 
                             xec::kDecodeDevListTiles, stream, S * m) == hipSuccess
              ? XEC_SUCCESS
              : XEC_DEVICE_ERROR;
+}
+
+// ---- repair and scrub ---------------------------------------------------------
+// xec_repair: the host scan lists every lost block, data and parity alike
+// (xec_scan_repair), and the launch is always work-list tiles, one reduction
+// per tile as encode: encode's residency table.  Up to kArgItems entries
+// travel in the kernel arguments; a longer list is staged in pinned memory and
+// goes through the caller's scratch on `stream` in pieces of what it holds
+// (copy a piece, rebuild it, copy the next: stream order keeps a copy behind
+// the kernel still reading the previous piece), as xec_decode_per_stripe's
+// fallback does.
+static xec_status repair_impl(void* d_data, void* d_parity, size_t S, size_t bs, size_t k,
+                              size_t m, const uint8_t* h_bitmap, uint8_t* d_bitmap,
+                              hipStream_t stream) {
+  g_repair_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  uint64_t n = 0;
+  uint32_t short_items[xec::kArgItems];
+  st = xec_scan_repair(h_bitmap, S, k, m, short_items, xec::kArgItems, &n);
+  if (st != XEC_SUCCESS || n == 0) return st;  // verdict from the scan alone: no device call
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, auto_occupancy(k / m));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (n <= xec::kArgItems) {
+    g_repair_tiling_used = XEC_TILING_ARG_LIST;
+    const hipError_t le = xec::launch_repair(d_data, d_parity, nullptr, g, ls,
+                                             xec::kRepairArgListTiles, stream, n, short_items);
+    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  }
+  if (d_bitmap == nullptr) return XEC_INVALID_SIZE;  // the list needs the scratch
+  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
+  if (!sd.ok()) return DEVERR(hipSuccess);
+  bool fault = false;
+  Staging* sg = stage_acquire(n * 4, sd.device(), &fault);
+  if (sg == nullptr) return DEVERR(hipSuccess);
+  uint32_t* items = static_cast<uint32_t*>(sg->host);
+  (void)xec_scan_repair(h_bitmap, S, k, m, items, n, &n);
+  g_repair_tiling_used = XEC_TILING_LIST;
+  const size_t pad = (4 - reinterpret_cast<uintptr_t>(d_bitmap) % 4) % 4;
+  const uint64_t cap = (S * (k + m) - pad) / 4;  // >= 255 here: n > 1,024 <= S*(k+m)
+  uint8_t* d_items = d_bitmap + pad;
+  bool queued = false;
+  hipError_t le = hipSuccess;
+  for (uint64_t q0 = 0; q0 < n && le == hipSuccess; q0 += cap) {
+    const uint64_t piece = n - q0 < cap ? n - q0 : cap;
+    le = hipMemcpyAsync(d_items, items + q0, piece * 4, hipMemcpyHostToDevice, stream);
+    queued |= le == hipSuccess;
+    if (le == hipSuccess)
+      le = xec::launch_repair(d_data, d_parity, d_items, g, ls, xec::kRepairListTiles, stream,
+                              piece);
+  }
+  stage_release(sg, queued, stream, false);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
+xec_status xec_repair(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
+                      const uint8_t* h_bitmap, uint8_t* d_bitmap, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  try {  // as xec_decode
+    return repair_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, stream);
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+int xec_repair_tiling_used(void) { return g_repair_tiling_used; }
+
+xec_status xec_repair_device(void* d_data, void* d_parity, size_t S, size_t bs, size_t k,
+                             size_t m, const uint8_t* d_bitmap, int32_t* d_status,
+                             hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_repair_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (d_bitmap == nullptr && S != 0) return XEC_INVALID_SIZE;
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  // No host view of the bitmap: class tiles, each doing the one reduction its
+  // class needs or none -- encode's tiling and residency table.
+  const xec::LaunchShape ls = launch_shape(bs, auto_occupancy(k / m));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_check(d_bitmap, g, d_status, stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  g_repair_tiling_used = XEC_TILING_CLASS;
+  return xec::launch_repair(d_data, d_parity, d_bitmap, g, ls, xec::kRepairClassTiles, stream) ==
+                 hipSuccess
+             ? XEC_SUCCESS
+             : XEC_DEVICE_ERROR;
+}
+
+// Residency of verify_kernel by class member count.  It has one more load per
+// lane than encode and no store stream, so encode's table was the start and
+// caps 1, 2, 4 and 8 were swept once at configs 2, 3 and 4 (k/m = 8, 16, 32;
+// tools/repair_scrub_bench.py --sweep, profiles/repair_scrub/): at 8 members
+// one wave per SIMD was 3.0 % faster than encode's 4 (83.9 against 86.5 us,
+// every round); at 16 encode's 2 tied with no cap and beat 1 and 4 by 3 %; at
+// 32 caps 1, 4 and 8 were within 0.5 %, inside the run-to-run spread, so
+// encode's 1 stays.  Member counts that were not swept keep encode's value.
+static int verify_auto_occupancy(uint64_t nm) { return nm == 8 ? 1 : auto_occupancy(nm); }
+
+xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (reinterpret_cast<uintptr_t>(d_count) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+  if (d_flags == nullptr && S != 0) return XEC_INVALID_SIZE;
+  if (d_count != nullptr &&
+      hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  if (hipMemsetAsync(d_flags, 0, S * m, stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  const xec::LaunchShape ls = launch_shape(bs, verify_auto_occupancy(k / m));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_verify(d_data, d_parity, d_flags, g, ls, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  if (d_count != nullptr &&
+      xec::launch_count_flags(d_flags, S * m, d_count, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  return XEC_SUCCESS;
 }
 
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,

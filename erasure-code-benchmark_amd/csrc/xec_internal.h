@@ -46,6 +46,19 @@ xec_status xec_scan_stripes(const uint8_t* h_bitmap, size_t S, size_t k, size_t 
                             uint8_t* codes, uint32_t* items, uint64_t cap, uint64_t* n_items,
                             uint64_t* failures);
 
+// Repair scan (xec_repair): lists EVERY lost block of the batch, data and
+// parity alike, as work items c << 8 | i with i in [0, k+m) -- i >= k is parity
+// block i - k -- in batch order; the first `cap` go to `items` (may be null with
+// cap 0) and *n_items is their total.  A block is lost iff its byte is 0; the
+// bit-0 rule of require_recovery plays no part.  XEC_DECODE_FAILURE if some
+// class of some stripe lost two blocks (is_recoverable; items and *n_items are
+// then unspecified), XEC_INVALID_COUNTS as xec_check_args, XEC_INVALID_SIZE
+// unless k + m <= kRepairItemMaxRow and S <= kWorkItemMaxStripes.  Defined in
+// xec_scan.cpp.
+constexpr size_t kRepairItemMaxRow = 256;
+xec_status xec_scan_repair(const uint8_t* h_bitmap, size_t S, size_t k, size_t m, uint32_t* items,
+                           uint64_t cap, uint64_t* n_items);
+
 // masks[c] = bit i set iff data byte i of stripe c's row is 0 (lost), for the
 // kernel-argument mask decode (xec_kernels.hip decode_argmask_kernel).
 // Requires k <= 32; the rows must already have passed xec_scan_bitmap (no

@@ -91,7 +91,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
   return hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, lds, s);
 }
 
-// The codec kernels (encode and every decode tiling) go through this: as
+// The codec kernels (encode, every decode and repair tiling, verify) go through this: as
 // launch(), but with the thread's pending kernel events, if any, recorded by
 // the kernel's dispatch itself and then cleared.
 template <typename... P>
@@ -150,6 +150,26 @@ inline uint32_t arg_items_capacity(uint64_t n) { return n <= 64 ? 64 : n <= 256 
 hipError_t launch_decode(void* d_data, const void* d_parity, const uint8_t* d_bitmap,
                          const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
                          uint64_t n_items = 0, const uint32_t* h_items = nullptr);
+// Repair tilings (xec_repair, xec_repair_device): every lost block, data or
+// parity, is rebuilt from the other members of its class.  Class: one tile per
+// (stripe, class, chunk), d_bitmap = the batch bitmap (any k, m; g.gate set by
+// xec_repair_device).  List / ArgList: one per (work item, chunk) as the decode
+// tilings of the same name, an item c << 8 | i with i in [0, k+m), i >= k
+// naming parity block i - k (k + m <= 256).
+constexpr int kRepairClassTiles = 0;
+constexpr int kRepairListTiles = 1;
+constexpr int kRepairArgListTiles = 2;
+hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
+                         const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
+                         uint64_t n_items = 0, const uint32_t* h_items = nullptr);
+// Scrub (xec_verify): class tiles; d_flags[c*m + j] = 1 where the XOR of class
+// j's data blocks and its parity block is nonzero anywhere (the caller zeroes
+// d_flags first, stream-ordered).  Reads the batch, writes only those bytes.
+hipError_t launch_verify(const void* d_data, const void* d_parity, uint8_t* d_flags,
+                         const Geometry& g, const LaunchShape& ls, hipStream_t s);
+// *d_count += the nonzero bytes among d_flags[0, n) (the caller zeroes it first).
+hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_count,
+                              hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

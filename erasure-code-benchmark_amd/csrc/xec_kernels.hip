@@ -405,6 +405,183 @@ __global__ __launch_bounds__(T) void decode_devlist_kernel(uint8_t* data,
 }
 
 // ---------------------------------------------------------------------------
+// repair (xec_repair, xec_repair_device): the recoverability rule is symmetric
+// -- a class has at most one lost block among its k/m data blocks and its
+// parity block -- so the lost block of a class, data or parity, is the XOR of
+// the class's other k/m blocks.  A lost data block is decode's reduction
+// (rebuild_item, stored sc1); a lost parity block is encode's reduction of
+// that class (stored nt).  Blocks that are present are never written.
+//
+// Work-list tiles: an item is c << 8 | i with i in [0, k+m) (k + m <= 256);
+// i >= k names parity block i - k.  The item is a scalar load, so the branch
+// between the two reductions is uniform.
+// ---------------------------------------------------------------------------
+template <int NM, int U, bool NT, int T>
+__device__ __forceinline__ void encode_class(const uint8_t* data, uint8_t* parity, uint64_t c,
+                                             uint64_t j, uint64_t chunk, const Geometry& g) {
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint8_t* base = data + (c * g.k + j) * g.bs;
+  uint8_t* dst = parity + (c * g.m + j) * g.bs;
+  const uint64_t off = (rotated(chunk, c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+  xor_members<NM, U, NT, T, kEncodeStoreAux>(base, g.m * g.bs, nullptr, -1, dst, off, g.bs, nm);
+}
+
+template <int NM, int U, bool NT, int T>
+__device__ __forceinline__ void repair_item(uint8_t* data, uint8_t* parity, uint32_t item,
+                                            uint64_t chunk, const Geometry& g) {
+  const uint32_t i = item & 0xFFu;
+  if (i < (uint32_t)g.k)
+    rebuild_item<NM, U, NT, T>(data, parity, item, chunk, g);
+  else
+    encode_class<NM, U, NT, T>(data, parity, item >> 8, i - (uint32_t)g.k, chunk, g);
+}
+
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void repair_list_kernel(uint8_t* data, uint8_t* parity,
+                                                        const uint32_t* __restrict__ items,
+                                                        Geometry g) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as decode_list_kernel
+    const uint32_t item = *(const_u32_as4)(items + t / g.tiles_per_block);
+    repair_item<NM, U, NT, T>(data, parity, item, t % g.tiles_per_block, g);
+  }
+}
+
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void repair_arglist_kernel(uint8_t* data, uint8_t* parity,
+                                                           Geometry g, ArgItems<CAP> items) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    repair_item<NM, U, NT, T>(data, parity, items.v[t / g.tiles_per_block],
+                              t % g.tiles_per_block, g);
+  }
+}
+
+// Class tiles over a device bitmap (xec_repair_device; gated on the check's
+// verdict): the workgroup reads its class's k/m data bitmap bytes and its
+// parity byte (scalar dword loads, as decode_class_kernel) and does the one
+// reduction the class needs, or none.  The check guarantees at most one loss
+// per class, so the first zero byte found is the only one.
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void repair_class_kernel(uint8_t* data, uint8_t* parity,
+                                                         const uint8_t* __restrict__ bitmap,
+                                                         Geometry g) {
+  if (g.gate != nullptr && *(const_i32_as4)g.gate != 0) return;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint64_t stride = g.m * g.bs;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as encode
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t row = reinterpret_cast<uint64_t>(bitmap + tc.c * (g.k + g.m));
+    if (sbyte(row + g.k + tc.j) == 0) {
+      encode_class<NM, U, NT, T>(data, parity, tc.c, tc.j, tc.chunk, g);
+      continue;
+    }
+    uint32_t lost = nm;
+    for (uint32_t r = 0; r < nm; ++r)
+      if (sbyte(row + tc.j + (uint64_t)r * g.m) == 0) { lost = r; break; }
+    if (lost == nm) continue;
+    uint8_t* base = data + (tc.c * g.k + tc.j) * g.bs;
+    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    xor_members<NM, U, NT, T, kDecodeStoreAux>(base, stride, parity + (tc.c * g.m + tc.j) * g.bs,
+                                               (int)lost, base + (uint64_t)lost * stride, off,
+                                               g.bs, nm);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// verify (xec_verify, the scrub): encode's tile, but the class's k/m data
+// blocks AND its parity block are XORed -- NM + 1 loads in flight per lane and
+// granule -- and nothing is stored but the verdict: a class whose bytes agree
+// reduces to zero everywhere.  reduce_members is xor_members without the store
+// (member NM of the class is the parity block at `extra`); it returns the OR
+// over this lane's U granules of the per-granule XOR, zero for granules past
+// the block's end.  One ballot per wave, one byte store by one lane where any
+// lane saw a nonzero byte; several tiles of a class may store the same 1.
+// ---------------------------------------------------------------------------
+template <int NM, int U, bool NT, int T>
+__device__ __forceinline__ u32x4 reduce_members(const uint8_t* base, uint64_t stride,
+                                                const uint8_t* extra, uint64_t off, uint64_t bs,
+                                                uint32_t nm_rt) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  u32x4 any = {0u, 0u, 0u, 0u};
+  if constexpr (NM > 0) {
+    if (off + (U - 1) * kStep < bs) {  // whole tile inside the block: no predication
+      u32x4 v[NM + 1][U];
+      const uint8_t* p = base + off;
+#pragma unroll
+      for (int r = 0; r < NM; ++r, p += stride) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = ld16<NT>(p + u * kStep);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[NM][u] = ld16<NT>(extra + off + u * kStep);
+      if constexpr (NM >= 32) __builtin_amdgcn_sched_barrier(0);  // as xor_members
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u32x4 acc = v[0][u];
+#pragma unroll
+        for (int r = 1; r <= NM; ++r) acc ^= v[r][u];
+        any |= acc;
+      }
+      return any;
+    }
+  }
+  // Ragged tail of a block, or a member count without a compiled unroll.
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : nm_rt;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t o = off + u * kStep;
+    if (o >= bs) continue;
+    u32x4 acc = ld16<NT>(extra + o);
+    uint32_t r = 0;
+    for (; r + 8 <= nm; r += 8) {
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = ld16<NT>(base + (uint64_t)(r + q) * stride + o);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc ^= v[q];
+    }
+    for (; r < nm; ++r) acc ^= ld16<NT>(base + (uint64_t)r * stride + o);
+    any |= acc;
+  }
+  return any;
+}
+
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void verify_kernel(const uint8_t* __restrict__ data,
+                                                   const uint8_t* __restrict__ parity,
+                                                   uint8_t* __restrict__ flags, Geometry g) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as encode
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t cls = tc.c * g.m + tc.j;
+    const uint8_t* base = data + (tc.c * g.k + tc.j) * g.bs;
+    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    const u32x4 v = reduce_members<NM, U, NT, T>(base, g.m * g.bs, parity + cls * g.bs, off, g.bs,
+                                                 (uint32_t)g.nm);
+    // every lane of the workgroup gets here: the tile loop is uniform
+    const uint64_t bad = __ballot((v.x | v.y | v.z | v.w) != 0u);
+    if (bad != 0 && (threadIdx.x & 63u) == 0) flags[cls] = 1;
+  }
+}
+
+// *count += nonzero bytes of flags[0, n) (xec_verify zeroes *count first,
+// stream-ordered): one atomicAdd per wave that found any.  A template (T =
+// threads per workgroup) so that it is emitted with the kernels above, after
+// the older ones.
+template <int T>
+__global__ __launch_bounds__(T) void count_flags_kernel(const uint8_t* __restrict__ flags,
+                                                        uint64_t n, uint32_t* count) {
+  uint32_t mine = 0;
+  for (uint64_t t = (uint64_t)blockIdx.x * T + threadIdx.x; t < n; t += (uint64_t)gridDim.x * T)
+    mine += flags[t] != 0;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
+  if ((threadIdx.x & 63u) == 0 && mine != 0) atomicAdd(count, mine);
+}
+
+// ---------------------------------------------------------------------------
 // check + list (xec_decode_device_list): one thread per (stripe, class), as
 // check_kernel, and a class that lost exactly one block, a data block, appends
 // its work item (c << 8 | i, xec_internal.h) after the list header.  A wave
@@ -737,6 +914,115 @@ hipError_t launch_fill(void* d_buf, uint64_t S, uint64_t words, uint64_t seed_ba
   if (gx == 0 || gy == 0) return hipSuccess;
   return launch(fill_kernel, dim3((uint32_t)gx, (uint32_t)gy), 256, 0, s,
                 static_cast<uint64_t*>(d_buf), S, words, seed_base);
+}
+
+// ---- repair and verify launchers (after every older launcher, so the older
+// kernels keep their place in the code object) ----------------------------
+namespace {
+
+template <int NM, int U, bool NT, int T>
+hipError_t launch_repair_t(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling,
+                           uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& al) {
+  uint8_t* dd = static_cast<uint8_t*>(d);
+  uint8_t* pp = static_cast<uint8_t*>(p);
+  if (tiling == kRepairArgListTiles) {
+    switch (arg_items_capacity(al.n)) {
+      case 64:
+        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 64>, grid, T, lds, s, dd, pp, g,
+                            arg_items<64>(al.items, al.n));
+      case 256:
+        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 256>, grid, T, lds, s, dd, pp, g,
+                            arg_items<256>(al.items, al.n));
+      default:
+        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, dd, pp, g,
+                            arg_items<1024>(al.items, al.n));
+    }
+  }
+  if (tiling == kRepairListTiles)
+    return launch_codec(repair_list_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp,
+                        reinterpret_cast<const uint32_t*>(bm), g);
+  return launch_codec(repair_class_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, bm, g);
+}
+
+template <int NM, int U, bool NT, int T>
+hipError_t launch_verify_t(const void* d, const void* p, uint8_t* flags, const Geometry& g,
+                           uint32_t grid, uint32_t lds, hipStream_t s) {
+  return launch_codec(verify_kernel<NM, U, NT, T>, grid, T, lds, s,
+                      static_cast<const uint8_t*>(d), static_cast<const uint8_t*>(p), flags, g);
+}
+
+template <int U, bool NT, int T>
+hipError_t rep_nm(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling,
+                  uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
+  XEC_NM_SWITCH(g.nm,
+                return (launch_repair_t<NM, U, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)))
+}
+
+template <int U, bool NT, int T>
+hipError_t ver_nm(const void* d, const void* p, uint8_t* flags, const Geometry& g, uint32_t grid,
+                  uint32_t lds, hipStream_t s) {
+  XEC_NM_SWITCH(g.nm, return (launch_verify_t<NM, U, NT, T>(d, p, flags, g, grid, lds, s)))
+}
+
+template <bool NT, int T>
+hipError_t rep_u(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling, int unroll,
+                 uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
+  return unroll == 2 ? rep_nm<2, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)
+                     : rep_nm<1, NT, T>(d, p, bm, g, tiling, grid, lds, s, a);
+}
+
+template <bool NT, int T>
+hipError_t ver_u(const void* d, const void* p, uint8_t* flags, const Geometry& g, int unroll,
+                 uint32_t grid, uint32_t lds, hipStream_t s) {
+  return unroll == 2 ? ver_nm<2, NT, T>(d, p, flags, g, grid, lds, s)
+                     : ver_nm<1, NT, T>(d, p, flags, g, grid, lds, s);
+}
+
+}  // namespace
+
+hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
+                         const Geometry& g_class, const LaunchShape& ls, int tiling,
+                         hipStream_t s, uint64_t n_items, const uint32_t* h_items) {
+  // class tiles (stripe, class, chunk) over the bitmap: repair_class_kernel;
+  // list tiles (entry, chunk): repair_list_kernel over the n_items entries
+  // d_bitmap holds, or repair_arglist_kernel over h_items passed by value
+  Geometry g = g_class;
+  if (tiling == kRepairListTiles || tiling == kRepairArgListTiles)
+    g.total_tiles = n_items * g.tiles_per_block;
+  if (g.total_tiles == 0) return hipSuccess;
+  if (g.k + g.m > 256 && tiling != kRepairClassTiles) return hipErrorInvalidValue;
+  if (tiling == kRepairArgListTiles && (n_items > kArgItems || h_items == nullptr))
+    return hipErrorInvalidValue;
+  const ArgList a{h_items, n_items};
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt
+               ? rep_u<true, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
+               : rep_u<false, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
+                                   a);
+  return ls.nt ? rep_u<true, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
+               : rep_u<false, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
+                                  a);
+}
+
+hipError_t launch_verify(const void* d_data, const void* d_parity, uint8_t* d_flags,
+                         const Geometry& g, const LaunchShape& ls, hipStream_t s) {
+  if (g.total_tiles == 0) return hipSuccess;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt ? ver_u<true, 256>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s)
+                 : ver_u<false, 256>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s);
+  return ls.nt ? ver_u<true, 64>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s)
+               : ver_u<false, 64>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s);
+}
+
+hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_count,
+                              hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t grid = grid_for((n + 255) / 256, 1024, 256);
+  return launch(count_flags_kernel<256>, grid, 256, 0, s, d_flags, n, d_count);
 }
 
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set

@@ -352,6 +352,46 @@ xec_status xec_scan_bitmap(const uint8_t* bm, size_t S, size_t k, size_t m, XecS
   return XEC_SUCCESS;
 }
 
+// ---- repair scan (xec_repair) -----------------------------------------------
+// Only zero bytes matter here (a block is lost iff its byte is 0), data and
+// parity alike, so the bitmap is searched flat for zero bytes, 8 at a time
+// (exact SWAR zero-byte test), and each hit is placed in its stripe by one
+// division.  Hits come in increasing position, so a class's mark is the
+// stripe (+1) that last lost a block of it: a second hit with the same mark
+// is the class's second loss.
+xec_status xec_scan_repair(const uint8_t* bm, size_t S, size_t k, size_t m, uint32_t* items,
+                           uint64_t cap, uint64_t* n_items) {
+  if (n_items) *n_items = 0;
+  if (k < 1 || m < 1 || k % m != 0) return XEC_INVALID_COUNTS;
+  if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  if (items == nullptr) cap = 0;
+  const size_t row = k + m, n = S * row;
+  std::vector<uint32_t> mark(m, 0);
+  uint64_t count = 0;
+  auto hit = [&](size_t pos) {
+    const size_t c = pos / row, i = pos - c * row;
+    const size_t cls = i < k ? i % m : i - k;
+    const uint32_t tag = static_cast<uint32_t>(c) + 1u;
+    if (mark[cls] == tag) return false;
+    mark[cls] = tag;
+    if (count < cap) items[count] = xec_work_item(c, i);
+    ++count;
+    return true;
+  };
+  constexpr uint64_t kLow7 = 0x7F7F7F7F7F7F7F7Full;
+  size_t pos = 0;
+  for (; pos + 8 <= n; pos += 8) {
+    const uint64_t w = load_u64(bm + pos);
+    uint64_t z = ~(((w & kLow7) + kLow7) | w | kLow7);  // 0x80 in every zero byte, exactly
+    for (; z; z &= z - 1)
+      if (!hit(pos + static_cast<size_t>(__builtin_ctzll(z) >> 3))) return XEC_DECODE_FAILURE;
+  }
+  for (; pos < n; ++pos)
+    if (bm[pos] == 0 && !hit(pos)) return XEC_DECODE_FAILURE;
+  if (n_items) *n_items = count;
+  return XEC_SUCCESS;
+}
+
 namespace {
 
 void loss_masks_scalar(const uint8_t* bm, size_t S, size_t k, size_t m, uint32_t* masks) {

@@ -9,11 +9,11 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     decode_arg_capacity_used, decode_device, decode_device_list,
                     decode_per_stripe, decode_tiling_used,
                     device_list_bytes, encode, erase,
-                    fill_splitmix64, init,
+                    fill_splitmix64, init, repair, repair_device, repair_tiling_used,
                     select_lost_blocks, set_decode_tiling, set_kernel_events, set_launch,
                     set_occupancy,
                     set_rotation, set_validate_kernel,
-                    status_string, validate_blocks, write_validation_pattern)
+                    status_string, validate_blocks, verify, write_validation_pattern)
 from .partition import stripe_range
 
 __all__ = [
@@ -21,9 +21,10 @@ __all__ = [
     "build_info", "check_args", "check_bitmap", "decode", "decode_arg_capacity_used",
     "decode_device", "decode_device_list",
     "decode_per_stripe", "decode_tiling_used", "device_list_bytes",
-    "encode", "erase", "fill_splitmix64", "init", "select_lost_blocks", "set_decode_tiling",
+    "encode", "erase", "fill_splitmix64", "init", "repair", "repair_device",
+    "repair_tiling_used", "select_lost_blocks", "set_decode_tiling",
     "set_kernel_events",
     "set_launch",
     "set_occupancy", "set_rotation", "set_validate_kernel", "status_string", "stripe_range", "validate_blocks",
-    "write_validation_pattern",
+    "verify", "write_validation_pattern",
 ]

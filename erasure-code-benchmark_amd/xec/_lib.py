@@ -30,6 +30,7 @@ EXPORTED = (
     "xec_decode_device_list", "xec_decode_device_list_bytes", "xec_get_tuning",
     "xec_set_tuning", "xec_set_rotation", "xec_select_lost_blocks",
     "xec_decode_arg_capacity_used", "xec_peer_link", "xec_set_kernel_events",
+    "xec_repair", "xec_repair_device", "xec_repair_tiling_used", "xec_verify",
 )
 
 
@@ -108,6 +109,10 @@ def lib() -> ctypes.CDLL:
         "xec_decode_device": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_decode_device_list": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, vp], st),
         "xec_decode_device_list_bytes": ([sz, sz, sz], sz),
+        "xec_repair": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_repair_device": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_repair_tiling_used": ([], ctypes.c_int),
+        "xec_verify": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

@@ -82,6 +82,38 @@ def device_list_bytes(S: int, k: int, m: int) -> int:
     return int(lib().xec_decode_device_list_bytes(S, k, m))
 
 
+def repair(d_data, d_parity, S: int, bs: int, k: int, m: int, h_bitmap, d_bitmap,
+           stream=None) -> Status:
+    """xec_repair -- every lost block, data or parity, rebuilt from the other
+    members of its class (host bitmap; all-or-nothing; k + m <= 256)."""
+    return Status(lib().xec_repair(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(h_bitmap),
+                                   _ptr(d_bitmap), _stream(stream)))
+
+
+def repair_device(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, d_status,
+                  stream=None) -> Status:
+    """xec_repair_device -- the same with the bitmap on the device; the batch
+    verdict lands in d_status (int32 device tensor: 0 or 4) in stream order."""
+    return Status(lib().xec_repair_device(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                          _ptr(d_bitmap), _ptr(d_status), _stream(stream)))
+
+
+def repair_tiling_used() -> int:
+    """xec_repair_tiling_used: the tiling this thread's last repair launched
+    (0 none, 2 class tiles, 3 list in d_bitmap, 4 list in the kernel arguments)."""
+    return int(lib().xec_repair_tiling_used())
+
+
+def verify(d_data, d_parity, S: int, bs: int, k: int, m: int, d_flags, d_count=None,
+           stream=None) -> Status:
+    """xec_verify -- the scrub: d_flags[c*m + j] (S*m device bytes) = 1 where
+    class j of stripe c no longer XORs to zero; d_count (device uint32,
+    optional) = how many classes are flagged."""
+    return Status(lib().xec_verify(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_flags),
+                                   _ptr(d_count) if d_count is not None else None,
+                                   _stream(stream)))
+
+
 def erase(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, stream=None) -> Status:
     """xec_erase -- device-side simulate_data_loss (abstract_bm.cpp:20-39)."""
     return Status(lib().xec_erase(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_bitmap),

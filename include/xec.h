@@ -94,7 +94,7 @@ xec_status xec_encode(const void* d_data, void* d_parity, size_t S, size_t bs, s
  * recovered, returns XEC_SUCCESS / XEC_DECODE_FAILURE from the host scan
  * before any device call, capturing or not, as the reference decides before
  * its first CUDA call (xorec_gpu_cmp.cu:75-81).
- * Lost parity is not regenerated.  Parity is READ-ONLY here, as in the CPU
+ * Lost parity is not regenerated (xec_repair does that).  Parity is READ-ONLY here, as in the CPU
  * decode (xorec.cpp:62-111) -- deliberately unlike the reference GPU decode,
  * which folds all data into parity (xorec_gpu_cmp.cu:94-102).  The content of
  * lost data blocks on entry is irrelevant (no zeroing pre-condition).
@@ -167,6 +167,71 @@ xec_status xec_decode_device_list(void* d_data, const void* d_parity, size_t S, 
  * and at most one 4-byte entry per parity class. */
 size_t xec_decode_device_list_bytes(size_t S, size_t k, size_t m);
 
+/* Full-stripe repair (no reference counterpart: neither reference decode puts
+ * lost parity back).  The recoverability rule is symmetric -- a class has at
+ * most one lost block among its k/m data blocks and its parity block -- so
+ * EVERY lost block, data or parity, is rebuilt as the XOR of the other k/m
+ * blocks of its class: a lost data block exactly as xec_decode rebuilds it, a
+ * lost parity block as xec_encode computes it.  Unlike xec_decode, d_parity is
+ * written (its lost blocks only).
+ * A block is lost iff its bitmap byte is 0 (2, 3, 255 are present): there is
+ * work iff some byte is 0 -- the bit-0 rule of require_recovery plays no part.
+ * All-or-nothing like xec_decode: if any class of any stripe lost two blocks
+ * the call returns XEC_DECODE_FAILURE and neither buffer is written.  What a
+ * lost block holds on entry is irrelevant; blocks that are present are never
+ * written.  h_bitmap, d_bitmap (scratch), argument checks and status codes as
+ * xec_decode.  The host scan lists the lost blocks as work items c << 8 | i,
+ * i in [0, k+m), i >= k naming parity block i - k, which requires k + m <= 256
+ * and S <= 2^24 (else XEC_INVALID_SIZE), and the launch is always work-list
+ * tiles: one per (listed block, 1 KiB chunk).  Up to 1,024 entries travel in
+ * the kernel arguments (capacities 64 / 256 / 1024) and nothing is copied; a
+ * longer list is staged in the pinned memory the library keeps and uploaded
+ * on `stream` itself into d_bitmap, in pieces of what the scratch holds (no
+ * copy stream of the library's is involved; a null d_bitmap is then
+ * XEC_INVALID_SIZE).  Nothing lost: XEC_SUCCESS without any device call; an
+ * unrecoverable batch: XEC_DECODE_FAILURE without any device call.  Not
+ * capturable, as xec_decode: on a capturing stream a call with blocks to
+ * rebuild returns XEC_DEVICE_ERROR with nothing queued. */
+xec_status xec_repair(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
+                      const uint8_t* h_bitmap, uint8_t* d_bitmap, hipStream_t stream);
+
+/* Device-resident form of xec_repair: no host work, so it can be captured in
+ * a hipGraph, and no limit on k + m or S.  Enqueues on `stream`: *d_status =
+ * 0; the check kernel of xec_decode_device (*d_status = 4 if any class of any
+ * stripe lost two blocks); then a repair kernel over class tiles (stripe,
+ * class, 1 KiB chunk) that does nothing if *d_status != 0 and otherwise reads
+ * its class's bitmap bytes and does the one reduction the class needs, or
+ * none.  Arguments, checks and the meaning of the return value and of
+ * *d_status as xec_decode_device; nothing is queued when an argument is
+ * rejected.  Bytes identical to xec_repair's. */
+xec_status xec_repair_device(void* d_data, void* d_parity, size_t S, size_t bs, size_t k,
+                             size_t m, const uint8_t* d_bitmap, int32_t* d_status,
+                             hipStream_t stream);
+
+/* Diagnostics: which tiling the calling thread's most recent xec_repair or
+ * xec_repair_device launched -- 0 none (an error, or nothing to rebuild),
+ * XEC_TILING_CLASS (xec_repair_device), XEC_TILING_LIST or XEC_TILING_ARG_LIST
+ * (xec_repair; enum below).  xec_decode_tiling_used is not affected. */
+int xec_repair_tiling_used(void);
+
+/* Device parity scrub (no reference counterpart): do data and parity still
+ * agree?  d_flags: S*m bytes of device memory owned by the caller, index
+ * c*m + j; d_count: one device uint32 (4-B aligned, else
+ * XEC_INVALID_ALIGNMENT), or NULL.  Enqueues on `stream` (no host work:
+ * capturable): d_flags zeroed by a stream-ordered memset; one kernel over
+ * class tiles that XORs the class's k/m data blocks and its parity block and
+ * sets d_flags[c*m + j] = 1 where any byte of the result is nonzero; then,
+ * when d_count is not NULL, a small kernel that sums the flags into *d_count
+ * (each class counted once).  Reads the whole batch once, (k+m)*bs*S bytes,
+ * and writes nothing but d_flags and *d_count -- no second parity buffer.
+ * A NULL d_flags with S > 0 is XEC_INVALID_SIZE; other checks as xec_encode;
+ * nothing is queued when an argument is rejected.
+ * What it cannot tell: WHICH block of a flagged class is at fault (a class's
+ * blocks enter the XOR alike), and two errors of one class that cancel -- the
+ * same bits flipped at the same offset of two of its blocks -- are invisible. */
+xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream);
+
 /* Host-only recoverability scan used by xec_decode (no GPU needed):
  * returns XEC_DECODE_FAILURE if some stripe is unrecoverable, else
  * XEC_SUCCESS and sets *needs_recovery to 1 iff some stripe needs recovery. */
@@ -234,7 +299,8 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * 0 = automatic (the default): the cap measured fastest for the member count
  * k/m at the default launch shape -- 1 at k/m = 32, 2 at 16, 4 at 4 and 8;
  * for other member counts none below 8, 4 below 20, 2 below 56, else 1;
- * none at 1 and 2.  The reserved LDS keeps other kernels' LDS
+ * none at 1 and 2.  The repair kernels take the same table;
+ * xec_verify too, except 1 at k/m = 8 (its own sweep).  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
  * 0..8. */
 xec_status xec_set_occupancy(int waves_per_simd);
@@ -314,8 +380,9 @@ int xec_decode_tiling_used(void);
 int xec_decode_arg_capacity_used(void);
 
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
- * xec_decode_per_stripe, xec_decode_device or xec_decode_device_list call
- * launches its encode / decode kernel with hipExtLaunchKernel and these two
+ * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
+ * xec_repair, xec_repair_device or xec_verify call
+ * launches its encode / decode / repair / verify kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
  * time, with no event packet queued between kernels (a hipEventRecord between
