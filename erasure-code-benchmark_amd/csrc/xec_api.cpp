@@ -15,6 +15,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -39,6 +40,7 @@ thread_local int g_arg_cap_used = 0;   // xec_decode_arg_capacity_used
 thread_local int g_tiling_used = 0;    // xec_decode_tiling_used: this thread's last xec_decode
 thread_local int g_rotation = 0;       // xec_set_rotation: 0 automatic, -1 none, > 0 tiles
 thread_local int g_repair_tiling_used = 0;  // xec_repair_tiling_used: this thread's last repair
+thread_local int g_update_tiling_used = 0;  // xec_update_tiling_used: this thread's last update
 
 constexpr size_t kBlockMultiple = 256;  // XOREC_BLOCK_SIZE_MULTIPLE
 constexpr size_t kMinBlock = 256;       // XOREC_MIN_BLOCK_SIZE
@@ -1191,6 +1193,121 @@ xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t
       xec::launch_count_flags(d_flags, S * m, d_count, stream) != hipSuccess)
     return XEC_DEVICE_ERROR;
   return XEC_SUCCESS;
+}
+
+// ---- in-place block update -----------------------------------------------------
+// xec_update / xec_update_device: parity[c][i % m] ^= data[c][i] ^ new, then
+// data[c][i] = new, for the named blocks only (xec_kernels.hip, update).  The
+// delta keeps a class's syndrome, so xec_verify still flags a class that was
+// already corrupt; a re-encode would not.  Residency is uncapped (a lane has
+// 3-5 loads in flight, the table's 1-2 members): caps 1, 2, 4 and 8 were swept
+// once with one block per stripe at configs 2, 3 and 4 (tools/update_bench.py
+// --sweep, profiles/update/) -- caps 1 and 2 cost 1.4-2.6x everywhere, 4 is
+// 7-16 % slower, 8 equals none.  (With the parity store still sc1, cap 4 was
+// 3 % faster at config 3 and 7 % and 5 % slower at configs 2 and 4.)  The order
+// of the checks is: initialisation, xec_check_args, nothing to do, then the new
+// buffer and the list -- all on the host before any device call.
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return na != 0 && nb != 0 && x < y + nb && y < x + na;
+}
+
+static xec_status update_check_new(const void* d_data, const void* d_parity, const void* d_new,
+                                   size_t new_bytes, size_t S, size_t bs, size_t k, size_t m) {
+  if (reinterpret_cast<uintptr_t>(d_new) % kAlign != 0) return XEC_INVALID_ALIGNMENT;
+  if (d_new == nullptr || ranges_overlap(d_new, new_bytes, d_data, S * k * bs) ||
+      ranges_overlap(d_new, new_bytes, d_parity, S * m * bs))
+    return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+static xec_status update_impl(void* d_data, void* d_parity, const void* d_new, size_t S,
+                              size_t bs, size_t k, size_t m, const uint32_t* h_items,
+                              size_t n, void* d_scratch, size_t scratch_bytes,
+                              hipStream_t stream) {
+  g_update_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (n == 0 || S == 0) return XEC_SUCCESS;
+  if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  st = update_check_new(d_data, d_parity, d_new, n * bs, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (h_items == nullptr) return XEC_INVALID_COUNTS;
+  for (size_t t = 0; t < n; ++t) {  // strictly ascending = batch order, no duplicates
+    const uint32_t it = h_items[t];
+    if ((it & 0xFFu) >= k || (it >> 8) >= S || (t > 0 && it <= h_items[t - 1]))
+      return XEC_INVALID_COUNTS;
+  }
+  const bool in_args = n <= xec::kArgItems;
+  if (!in_args) {
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+    if (d_scratch == nullptr || scratch_bytes < xec_update_scratch_bytes(n))
+      return XEC_INVALID_SIZE;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_update_tiling_used = XEC_TILING_ARG_LIST;
+    const hipError_t le = xec::launch_update(d_data, d_parity, d_new, nullptr, g, ls,
+                                             xec::kUpdateArgListTiles, stream, n, h_items);
+    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  }
+  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
+  if (!sd.ok()) return DEVERR(hipSuccess);
+  bool fault = false;
+  Staging* sg = stage_acquire(n * 4, sd.device(), &fault);
+  if (sg == nullptr) return DEVERR(hipSuccess);
+  std::memcpy(sg->host, h_items, n * 4);
+  g_update_tiling_used = XEC_TILING_LIST;
+  hipError_t le = hipMemcpyAsync(d_scratch, sg->host, n * 4, hipMemcpyHostToDevice, stream);
+  const bool queued = le == hipSuccess;
+  if (queued)
+    le = xec::launch_update(d_data, d_parity, d_new, d_scratch, g, ls, xec::kUpdateListTiles,
+                            stream, n);
+  stage_release(sg, queued, stream, false);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
+xec_status xec_update(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                      size_t k, size_t m, const uint32_t* h_items, size_t n_items,
+                      void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  try {  // as xec_decode
+    return update_impl(d_data, d_parity, d_new, S, bs, k, m, h_items, n_items, d_scratch,
+                       scratch_bytes, stream);
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+size_t xec_update_scratch_bytes(size_t n_items) { return 4 * n_items; }
+
+int xec_update_tiling_used(void) { return g_update_tiling_used; }
+
+xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, size_t S,
+                             size_t bs, size_t k, size_t m, const uint8_t* d_mask,
+                             hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_update_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  // every argument is checked before any work is queued on the stream
+  if (d_mask == nullptr) return XEC_INVALID_SIZE;
+  st = update_check_new(d_data, d_parity, d_new, S * k * bs, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // No host view of the mask: class tiles, each folding its class's marked
+  // members or doing nothing.
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  g_update_tiling_used = XEC_TILING_CLASS;
+  return xec::launch_update(d_data, d_parity, d_new, d_mask, g, ls, xec::kUpdateClassTiles,
+                            stream) == hipSuccess
+             ? XEC_SUCCESS
+             : XEC_DEVICE_ERROR;
 }
 
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,

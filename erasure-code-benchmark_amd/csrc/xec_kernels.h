@@ -91,9 +91,9 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
   return hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, lds, s);
 }
 
-// The codec kernels (encode, every decode and repair tiling, verify) go through this: as
-// launch(), but with the thread's pending kernel events, if any, recorded by
-// the kernel's dispatch itself and then cleared.
+// The codec kernels (encode, every decode, repair and update tiling, verify)
+// go through this: as launch(), but with the thread's pending kernel events,
+// if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
                         typename NoDeduce<P>::type... args) {
@@ -160,6 +160,21 @@ constexpr int kRepairClassTiles = 0;
 constexpr int kRepairListTiles = 1;
 constexpr int kRepairArgListTiles = 2;
 hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
+                         const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
+                         uint64_t n_items = 0, const uint32_t* h_items = nullptr);
+// Update tilings (xec_update, xec_update_device): data block i of stripe c takes
+// a new block and parity[c][i % m] ^= old ^ new; one tile folds every updated
+// member of its (stripe, class, chunk), so each parity granule has one writer.
+// Class: one tile per (stripe, class, chunk), d_sel = the S*k mask bytes
+// (nonzero = take the block), d_new mirrors d_data (any k, S).  List / ArgList:
+// one per (list position, chunk) over items c << 8 | i (i < k <= 256), strictly
+// ascending (the caller checked), d_new = the new blocks packed in list order;
+// d_sel = the n_items u32 items on the device (4-byte aligned), or h_items
+// passed by value (at most kArgItems).  No member-count template parameter.
+constexpr int kUpdateClassTiles = 0;
+constexpr int kUpdateListTiles = 1;
+constexpr int kUpdateArgListTiles = 2;
+hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
                          const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
                          uint64_t n_items = 0, const uint32_t* h_items = nullptr);
 // Scrub (xec_verify): class tiles; d_flags[c*m + j] = 1 where the XOR of class

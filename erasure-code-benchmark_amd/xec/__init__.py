@@ -13,7 +13,8 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     select_lost_blocks, set_decode_tiling, set_kernel_events, set_launch,
                     set_occupancy,
                     set_rotation, set_validate_kernel,
-                    status_string, validate_blocks, verify, write_validation_pattern)
+                    status_string, update, update_device, update_scratch_bytes,
+                    update_tiling_used, validate_blocks, verify, write_validation_pattern)
 from .partition import stripe_range
 
 __all__ = [
@@ -25,6 +26,7 @@ __all__ = [
     "repair_tiling_used", "select_lost_blocks", "set_decode_tiling",
     "set_kernel_events",
     "set_launch",
-    "set_occupancy", "set_rotation", "set_validate_kernel", "status_string", "stripe_range", "validate_blocks",
+    "set_occupancy", "set_rotation", "set_validate_kernel", "status_string", "stripe_range",
+    "update", "update_device", "update_scratch_bytes", "update_tiling_used", "validate_blocks",
     "verify", "write_validation_pattern",
 ]

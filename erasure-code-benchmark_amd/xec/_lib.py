@@ -31,6 +31,7 @@ EXPORTED = (
     "xec_set_tuning", "xec_set_rotation", "xec_select_lost_blocks",
     "xec_decode_arg_capacity_used", "xec_peer_link", "xec_set_kernel_events",
     "xec_repair", "xec_repair_device", "xec_repair_tiling_used", "xec_verify",
+    "xec_update", "xec_update_device", "xec_update_scratch_bytes", "xec_update_tiling_used",
 )
 
 
@@ -113,6 +114,10 @@ def lib() -> ctypes.CDLL:
         "xec_repair_device": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_repair_tiling_used": ([], ctypes.c_int),
         "xec_verify": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_update": ([vp, vp, vp, sz, sz, sz, sz, vp, sz, vp, sz, vp], st),
+        "xec_update_device": ([vp, vp, vp, sz, sz, sz, sz, vp, vp], st),
+        "xec_update_scratch_bytes": ([sz], sz),
+        "xec_update_tiling_used": ([], ctypes.c_int),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

@@ -114,6 +114,36 @@ def verify(d_data, d_parity, S: int, bs: int, k: int, m: int, d_flags, d_count=N
                                    _stream(stream)))
 
 
+def update(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, h_items, n_items: int,
+           d_scratch=None, scratch_bytes: int = 0, stream=None) -> Status:
+    """xec_update -- in place: block i of stripe c takes the t-th block of d_new
+    and parity[c][i % m] ^= old ^ new, for the n_items host items c << 8 | i
+    (uint32, strictly ascending).  d_scratch (update_scratch_bytes(n_items)
+    device bytes) is needed only past 1,024 items."""
+    return Status(lib().xec_update(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs, k, m,
+                                   _ptr(h_items), n_items, _ptr(d_scratch), scratch_bytes,
+                                   _stream(stream)))
+
+
+def update_device(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, d_mask,
+                  stream=None) -> Status:
+    """xec_update_device -- the same with a device mask (S*k bytes, NONZERO =
+    take the block) and d_new a shadow of d_data's layout; capturable."""
+    return Status(lib().xec_update_device(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs, k, m,
+                                          _ptr(d_mask), _stream(stream)))
+
+
+def update_scratch_bytes(n_items: int) -> int:
+    """xec_update_scratch_bytes: 4 * n_items."""
+    return int(lib().xec_update_scratch_bytes(n_items))
+
+
+def update_tiling_used() -> int:
+    """xec_update_tiling_used: the tiling this thread's last update launched
+    (0 none, 2 class tiles, 3 list in d_scratch, 4 list in the kernel arguments)."""
+    return int(lib().xec_update_tiling_used())
+
+
 def erase(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, stream=None) -> Status:
     """xec_erase -- device-side simulate_data_loss (abstract_bm.cpp:20-39)."""
     return Status(lib().xec_erase(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_bitmap),

@@ -226,11 +226,89 @@ int xec_repair_tiling_used(void);
  * and writes nothing but d_flags and *d_count -- no second parity buffer.
  * A NULL d_flags with S > 0 is XEC_INVALID_SIZE; other checks as xec_encode;
  * nothing is queued when an argument is rejected.
+ * Captured in a hipGraph the two memsets become memset nodes.  Open
+ * observation (cause not found; tools/lab/graph_verify_probe.py, DESIGN.md §3
+ * *Update*): where the process allocated device memory, uploaded from pageable
+ * host memory or captured another graph around the capture, replays have left
+ * d_flags and *d_count with bytes no kernel stores, on a batch that was right.
+ * With every input on the device before the capture and only device-to-device
+ * copies between replays the captured scrub has been exact.
  * What it cannot tell: WHICH block of a flagged class is at fault (a class's
  * blocks enter the XOR alike), and two errors of one class that cancel -- the
  * same bits flipped at the same offset of two of its blocks -- are invisible. */
 xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                       size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream);
+
+/* In-place block update, the small write of a parity store (no reference
+ * counterpart: its codec encodes and decodes whole stripes).  Data block i of
+ * stripe c is replaced by a new block and the parity of its class follows by
+ * the delta,
+ *     parity[c][i % m] ^= data[c][i] ^ new;    data[c][i] = new
+ * -- three block reads and two block writes per changed block, against the
+ * k + m blocks per stripe of the xec_encode that would otherwise put parity
+ * right (5/17 of its bytes for one block of a 16+1 stripe, and nothing for a
+ * stripe nobody wrote).  Blocks that are not named are neither read nor
+ * written, except the parity block of a class with an item, which is read and
+ * written.  One workgroup owns a parity granule for the whole call and folds
+ * every item of its class, so several items of one class in one call are fine.
+ * The delta keeps a class's syndrome: a class whose data and parity disagreed
+ * before the call disagrees after it, and xec_verify still flags it, where a
+ * re-encode would silently bless the damage.
+ * When not to use it: updating g members of one class reads 2g + 1 blocks, a
+ * re-encode of that class k/m; past g > (k/m - 1) / 2 xec_encode moves fewer
+ * bytes.  The library does not switch for the caller -- that would drop the
+ * syndrome.
+ *
+ * h_items[t] = c << 8 | i with i < k and c < S, n_items of them, strictly
+ * ascending (batch order; no duplicates); anything else is XEC_INVALID_COUNTS.
+ * The packing needs k <= 256 and S <= 2^24, else XEC_INVALID_SIZE.  The new
+ * content of item t is the bs bytes at d_new + t*bs (packed in list order);
+ * d_new must be 64-byte aligned (XEC_INVALID_ALIGNMENT) and its n_items*bs
+ * bytes must overlap neither the data nor the parity range (XEC_INVALID_SIZE,
+ * as is a NULL d_new).  Order of the checks: XEC_NOT_INITIALIZED, then
+ * xec_check_args; n_items == 0 or S == 0 is then XEC_SUCCESS without a device
+ * call; then the above, all decided on the host before any device call, so a
+ * rejected call queues nothing and changes nothing.  h_items is read before
+ * the call returns; the call is asynchronous on `stream`.
+ * Up to 1,024 items travel in the kernel arguments (capacities 64 / 256 /
+ * 1024): nothing is copied and d_scratch may be NULL.  A longer list is staged
+ * in the pinned memory the library keeps and uploaded on `stream` itself into
+ * d_scratch in one copy: d_scratch must then be 4-byte aligned
+ * (XEC_INVALID_ALIGNMENT), not NULL and of at least
+ * xec_update_scratch_bytes(n_items) bytes (XEC_INVALID_SIZE).  Not capturable,
+ * as xec_repair: on a capturing stream a call with work returns
+ * XEC_DEVICE_ERROR with nothing queued. */
+xec_status xec_update(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                      size_t k, size_t m, const uint32_t* h_items, size_t n_items,
+                      void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+
+/* Scratch bytes xec_update needs for a list of n_items: 4 * n_items. */
+size_t xec_update_scratch_bytes(size_t n_items);
+
+/* Device-resident form of xec_update: no host work, so it can be captured in a
+ * hipGraph (a replay applies whatever the mask and d_new hold at replay
+ * time), and no limit on k or S.  d_mask: S*k device bytes, index c*k + i;
+ * NONZERO means "take the new block" -- the opposite sense of the loss
+ * bitmaps, where 0 marks the block to act on.  d_new mirrors d_data's layout
+ * (a shadow buffer of S*k*bs bytes, block i of stripe c at (c*k + i)*bs); only
+ * its marked blocks are read.  One kernel over class tiles (stripe, class,
+ * 1 KiB chunk): a tile scans its class's k/m mask bytes, folds the marked
+ * members and writes nothing where none is marked.  There is no verdict: an
+ * update cannot be unrecoverable.  A NULL d_mask with S > 0 is
+ * XEC_INVALID_SIZE; d_new's alignment and overlap (over S*k*bs bytes),
+ * xec_check_args and initialisation as xec_update; nothing is queued when an
+ * argument is rejected.  Bytes identical to xec_update's with the same set of
+ * blocks. */
+xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, size_t S,
+                             size_t bs, size_t k, size_t m, const uint8_t* d_mask,
+                             hipStream_t stream);
+
+/* Diagnostics: which tiling the calling thread's most recent xec_update or
+ * xec_update_device launched -- 0 none (an error, or an empty update),
+ * XEC_TILING_ARG_LIST or XEC_TILING_LIST (xec_update), XEC_TILING_CLASS
+ * (xec_update_device; enum below).  xec_decode_tiling_used and
+ * xec_repair_tiling_used are not affected. */
+int xec_update_tiling_used(void);
 
 /* Host-only recoverability scan used by xec_decode (no GPU needed):
  * returns XEC_DECODE_FAILURE if some stripe is unrecoverable, else
@@ -300,7 +378,8 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * k/m at the default launch shape -- 1 at k/m = 32, 2 at 16, 4 at 4 and 8;
  * for other member counts none below 8, 4 below 20, 2 below 56, else 1;
  * none at 1 and 2.  The repair kernels take the same table;
- * xec_verify too, except 1 at k/m = 8 (its own sweep).  The reserved LDS keeps other kernels' LDS
+ * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels run
+ * uncapped at every k/m (their own sweep).  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
  * 0..8. */
 xec_status xec_set_occupancy(int waves_per_simd);
@@ -381,8 +460,8 @@ int xec_decode_arg_capacity_used(void);
 
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
- * xec_repair, xec_repair_device or xec_verify call
- * launches its encode / decode / repair / verify kernel with hipExtLaunchKernel and these two
+ * xec_repair, xec_repair_device, xec_verify, xec_update or xec_update_device call
+ * launches its encode / decode / repair / verify / update kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
  * time, with no event packet queued between kernels (a hipEventRecord between

@@ -1,0 +1,86 @@
+"""ISA-level invariants of the update kernels (CPU only: hipcc cross-compiles;
+the listing is `make asm`'s, as tests/test_isa.py and tests/test_isa_repair.py
+read it).
+
+* every 16-byte load of a non-temporal (NT=true) instantiation carries `nt`;
+* every 16-byte store of an NT=true instantiation carries exactly one explicit
+  policy, `nt` or `sc1`: the new data block and the parity block are both
+  stored in place through st16_block, never by a plain store.  The NT=false
+  instantiations (xec_set_launch cache_policy 2) store plainly by design, as
+  tests/test_isa_repair.py has it, and are only checked to hold stores;
+* every instantiation holds loads and stores (it reads old, new and parity and
+  writes data and parity);
+* the kernels take no member-count parameter, so there are <U, NT, T> = 8 of
+  the class kernel, 8 of the list kernel and 8 x 3 capacities of the
+  argument-list kernel.
+"""
+from __future__ import annotations
+
+import re
+import subprocess
+
+import pytest
+
+from conftest import PKG_DIR
+
+ASM = PKG_DIR / "build" / "xec_kernels-gfx950.s"
+KINDS = {"update_list": 8, "update_arglist": 24, "update_class": 8}
+
+
+@pytest.fixture(scope="module")
+def kernels() -> dict[str, dict]:
+    subprocess.run(["make", "-C", str(PKG_DIR), "asm"], check=True, capture_output=True)
+    text = ASM.read_text()
+    out = {}
+    for m in re.finditer(r"^(_ZN3xec[12][0-9](?:update_list|update_arglist|update_class)"
+                         r"_kernel\w+):.*?^\s*s_endpgm", text, re.S | re.M):
+        out[m.group(1)] = {"body": m.group(0)}
+    # 2 unrolls x 2 policies x 2 workgroup sizes, arglist x 3 capacities; no member count
+    assert len(out) == sum(KINDS.values()), f"{len(out)} update instantiations in the ISA"
+    return out
+
+
+def _nt(name: str) -> bool:
+    # template args <U, NT, T>: ...ILi1ELb1ELi64E...
+    return re.search(r"ELb1E", name) is not None
+
+
+def _loads16(body):
+    return re.findall(r"^\s*((?:global|buffer)_load_dwordx4[^\n]*)", body, re.M)
+
+
+def _stores16(body):
+    return re.findall(r"^\s*((?:global|buffer|flat|scratch)_store_dwordx4[^\n]*)", body, re.M)
+
+
+def test_instantiation_count_is_the_template_set(kernels):
+    for kind, want in KINDS.items():
+        hits = [n for n in kernels if re.search(rf"\d\d{kind}_kernelI", n)]
+        assert len(hits) == want, (kind, len(hits))
+        assert sum(_nt(n) for n in hits) == want // 2, kind
+        # <U, NT, T>: the first template argument is the unroll, 1 or 2 -- no NM ahead of it
+        for n in hits:
+            assert re.search(rf"{kind}_kernelILi[12]ELb[01]ELi(?:64|256)E", n), n
+
+
+def test_nt_instantiations_load_nt(kernels):
+    for name, k in kernels.items():
+        loads = _loads16(k["body"])
+        assert loads, name
+        if not _nt(name):
+            continue
+        missing = [i for i in loads if not re.search(r"\bnt\b", i)]
+        assert not missing, f"{name}: {missing[:3]}"
+
+
+def test_stores_carry_exactly_one_explicit_policy(kernels):
+    for name, k in kernels.items():
+        stores = _stores16(k["body"])
+        assert stores, name
+        if not _nt(name):
+            continue
+        both = [i for i in stores if re.search(r"\bnt\b", i) and re.search(r"\bsc1\b", i)]
+        plain = [i for i in stores if not re.search(r"\b(nt|sc1)\b", i)]
+        assert not both and not plain, f"{name}: {(both + plain)[:3]}"
+        # st16_block's buffer store, never a global or flat one
+        assert all(i.startswith("buffer_store_dwordx4") for i in stores), name
