@@ -1310,6 +1310,109 @@ xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, si
              : XEC_DEVICE_ERROR;
 }
 
+// ---- block digests and locate ----------------------------------------------------
+// digest(block) = sum over its u64 words of splitmix_at(w[n], n) mod 2^64
+// (xec_kernels.h); xec_digest_host is that sentence on the host.
+uint64_t xec_digest_host(const void* block, size_t bs) {
+  const unsigned char* p = static_cast<const unsigned char*>(block);
+  uint64_t sum = 0;
+  for (size_t n = 0; n < bs / 8; ++n) {
+    uint64_t w = 0;
+    for (int b = 7; b >= 0; --b) w = (w << 8) | p[8 * n + (size_t)b];  // little-endian
+    sum += xec::splitmix_at(w, n);
+  }
+  return sum;
+}
+
+// Launch shape of digest_kernel, swept once at configs 2, 3 and 4
+// (tools/digest_bench.py --sweep, profiles/digest/; kernel times in us at
+// config 2 / 3 / 4).  A lane has 8 loads in flight whatever k/m is, so there
+// is one choice, not a table.
+//  * Residency: no cap.  None 96.6 / 669.7 / 1717; cap 1 115.0 / 826.3 / 4926,
+//    cap 2 98.9 / 669.4 / 2706, cap 4 96.2 / 668.5 / 1789, cap 8 = none (the
+//    kernel's registers admit 4 waves per SIMD): a cap only loses, most at
+//    config 4, whose one-tile blocks need every wave to cover their loads.
+//  * Loads: nt (the library's default policy).  Default loads were 8 % slower
+//    at config 2 (104.7), 11 % at config 3 (741.0), 2 % at config 4 (1759).
+//  * Grid: at most kDigestMaxGrid workgroups, walking the tiles in grid
+//    strides.  One workgroup per tile is the same at configs 2 and 3 (9,216 and
+//    69,632 tiles: 96.7 / 668.3 against 96.1 / 669.5) but config 4 has 2.16
+//    million 4 KiB tiles, and 131,072 workgroups ran them in 1559 against 1775
+//    (full digest) and 457 against 704 (locate over the flags of 1 damaged
+//    stripe in 9); 32,768: 1585 / 463, 8,192: 1626 / 483 and 1-4 % slower at
+//    config 3, 2,048: 2146 / 858.
+// The segment (kDigestSegmentBytes, xec_kernels.h): 16 KiB was 1.117 x verify
+// at config 3 where 64 KiB was 1.070 and 256 KiB 1.067 (config 2 is one
+// segment from 64 KiB on, config 4 always), so 64 KiB, which keeps more
+// workgroups per block for small batches.
+constexpr uint32_t kDigestMaxGrid = 131072;
+
+static xec::LaunchShape digest_launch_shape(size_t bs) {
+  xec::LaunchShape ls = launch_shape(bs, 0);
+  if (ls.max_grid == 0) ls.max_grid = kDigestMaxGrid;
+  return ls;
+}
+
+// The checks xec_digest and xec_locate share, in the order include/xec.h
+// gives; d_work, d_bitmap and d_count are xec_locate's (locate = false: xec_digest).
+static xec_status digest_check(const void* d_data, const void* d_parity, size_t S, size_t bs,
+                               size_t k, size_t m, const void* d_digests, const void* d_work,
+                               size_t work_bytes, bool locate, const void* d_bitmap,
+                               const void* d_count) {
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  const xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S != 0 && d_digests == nullptr) return XEC_INVALID_SIZE;
+  if (locate && ((S != 0 && d_work == nullptr) || work_bytes < xec_locate_work_bytes(S, k, m)))
+    return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_digests) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(d_work) % 8 != 0 || reinterpret_cast<uintptr_t>(d_count) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (locate && S != 0 && d_bitmap == nullptr) return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+xec_status xec_digest(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, const uint8_t* d_select, uint64_t* d_digests,
+                      hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  const xec_status st = digest_check(d_data, d_parity, S, bs, k, m, d_digests, nullptr, 0, false,
+                                     nullptr, nullptr);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  const xec::LaunchShape ls = digest_launch_shape(bs);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  const hipError_t e = xec::launch_digest(d_data, d_parity, d_select,
+                                          d_select ? xec::kDigestSelect : xec::kDigestAll,
+                                          d_digests, g, ls, stream);
+  return e == hipSuccess ? XEC_SUCCESS : DEVERR(e);
+}
+
+size_t xec_locate_work_bytes(size_t S, size_t k, size_t m) { return 8 * S * (k + m); }
+
+xec_status xec_locate(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, const uint64_t* d_digests, const uint8_t* d_flags,
+                      uint8_t* d_bitmap, uint32_t* d_count, void* d_work, size_t work_bytes,
+                      hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  const xec_status st = digest_check(d_data, d_parity, S, bs, k, m, d_digests, d_work, work_bytes,
+                                     true, d_bitmap, d_count);
+  if (st != XEC_SUCCESS) return st;
+  if (d_count != nullptr &&
+      hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  const xec::LaunchShape ls = digest_launch_shape(bs);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  uint64_t* fresh = static_cast<uint64_t*>(d_work);
+  hipError_t e = xec::launch_digest(d_data, d_parity, d_flags,
+                                    d_flags ? xec::kDigestFlags : xec::kDigestAll, fresh, g, ls,
+                                    stream);
+  if (e == hipSuccess)
+    e = xec::launch_locate_compare(fresh, d_digests, d_flags, d_bitmap, d_count, g, stream);
+  return e == hipSuccess ? XEC_SUCCESS : DEVERR(e);
+}
+
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
   if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;

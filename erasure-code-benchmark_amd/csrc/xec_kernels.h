@@ -57,6 +57,23 @@ inline uint32_t grid_for(uint64_t work_items, uint32_t max_grid, uint32_t thread
   return (uint32_t)(grid ? grid : 1);
 }
 
+// splitmix64.  splitmix_at(seed, n) is output n of the stream whose state
+// starts at `seed` (xec_fill_splitmix64), and the term of word n of a block in
+// its digest (xec_digest, include/xec.h): for fixed n a bijection of `seed`.
+// splitmix_mix is the finaliser alone, for callers that keep (n+1)*golden as a
+// running sum.  Host and device: xec_digest_host is the same code.
+constexpr uint64_t kSplitmixGolden = 0x9E3779B97F4A7C15ull;
+
+__host__ __device__ __forceinline__ uint64_t splitmix_mix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__host__ __device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t n) {
+  return splitmix_mix(seed + (n + 1) * kSplitmixGolden);
+}
+
 // Test hook: XEC_TEST_FAIL_LAUNCH=1 in the environment (read once) makes every
 // kernel launch of the library invalid (2048 threads per workgroup), so that a
 // test sees the wrappers report a genuine launch failure while an error of the
@@ -91,8 +108,8 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
   return hipLaunchKernel(reinterpret_cast<const void*>(kernel), grid, block, argv, lds, s);
 }
 
-// The codec kernels (encode, every decode, repair and update tiling, verify)
-// go through this: as launch(), but with the thread's pending kernel events,
+// The codec kernels (encode, every decode, repair and update tiling, verify,
+// digest) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -185,6 +202,30 @@ hipError_t launch_verify(const void* d_data, const void* d_parity, uint8_t* d_fl
 // *d_count += the nonzero bytes among d_flags[0, n) (the caller zeroes it first).
 hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_count,
                               hipStream_t s);
+// Block digests (xec_digest, xec_locate): d_out[c*(k+m) + i] = the digest of
+// block i of stripe c (i >= k: parity block i - k) for every wanted block;
+// other slots are neither read nor written.  The wanted slots are zeroed here
+// first (a memset for kDigestAll, else a small kernel), then one kernel over
+// (block, segment) tiles adds each segment's sum into its slot with one
+// atomicAdd.  Of ls only threads, nt, max_grid and lds_bytes apply.
+//   kDigestAll     every block (d_gate unused);
+//   kDigestSelect  d_gate = S*(k+m) bytes, nonzero = wanted;
+//   kDigestFlags   d_gate = xec_verify's S*m flags, a block is wanted iff its
+//                  class's flag is nonzero.
+// The segment size was swept once (16, 64 and 256 KiB; the figures stand with
+// the launch shape in xec_api.cpp digest_launch_shape, DESIGN.md §3 *Locate*).
+constexpr int kDigestAll = 0;
+constexpr int kDigestSelect = 1;
+constexpr int kDigestFlags = 2;
+constexpr uint64_t kDigestSegmentBytes = 64u << 10;
+hipError_t launch_digest(const void* d_data, const void* d_parity, const uint8_t* d_gate, int mode,
+                         uint64_t* d_out, const Geometry& g, const LaunchShape& ls, hipStream_t s);
+// d_bitmap[b] = 0 where slot b was checked (d_flags == nullptr: every slot,
+// else its class's flag nonzero) and d_fresh[b] != d_stored[b], else 1;
+// *d_count (may be nullptr; the caller zeroes it first) += the zeros written.
+hipError_t launch_locate_compare(const uint64_t* d_fresh, const uint64_t* d_stored,
+                                 const uint8_t* d_flags, uint8_t* d_bitmap, uint32_t* d_count,
+                                 const Geometry& g, hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

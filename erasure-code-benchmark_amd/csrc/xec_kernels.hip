@@ -837,13 +837,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint8_t* __restrict__
 // ---------------------------------------------------------------------------
 // fill: splitmix64 stream per stripe, state seed_base + c
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t n) {
-  uint64_t z = seed + (n + 1) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// splitmix_at(seed, n): xec_kernels.h (the block digest shares it, on the
+// device and on the host).
 __global__ __launch_bounds__(256) void fill_kernel(uint64_t* buf, uint64_t S, uint64_t words,
                                                    uint64_t seed_base) {
   for (uint64_t c = blockIdx.y; c < S; c += gridDim.y) {
@@ -1246,6 +1241,182 @@ hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const 
                                  s, a)
                : upd_u<false, 64>(d_data, d_parity, d_new, d_sel, g, tiling, ls.unroll, grid, lds,
                                   s, a);
+}
+
+// ---------------------------------------------------------------------------
+// digest and locate (xec_digest, xec_locate).  Kernels and launchers together,
+// after every older one, so the older kernels keep their place.
+//
+//   digest(block) = sum over its u64 words w[n] of splitmix_at(w[n], n)  (mod 2^64)
+//
+// The sum is associative and commutative, so any split of a block over lanes,
+// waves, workgroups and atomic adds gives the same bits.  A tile is one
+// SEGMENT of one block -- kDigestSegmentBytes (xec_kernels.h), not a 1 KiB
+// chunk: the workgroup walks it with 16-byte loads, each lane keeps its sum in
+// registers, the workgroup reduces with shuffles and ONE lane does ONE 64-bit
+// atomicAdd into the block's slot, so a 1 MiB block collects 16 adds where 1 KiB
+// tiles would send 1,024 to one address (atomics run at the memory side and
+// slow down ~14x when every adder hits one row, MI355X_MICROARCH.md).  The
+// caller zeroes the slots first, stream-ordered.
+//
+// A lane keeps (n + 1) * golden as a running sum: its word index advances by
+// 2 * T per step, so that is one 64-bit add, and the two 64-bit multiplies per
+// word are splitmix_mix's own.
+//
+// Which blocks: slot b = c*(k+m) + i, the bitmap's layout.  kDigestAll: every
+// block.  kDigestSelect: gate[b] != 0.  kDigestFlags: gate = xec_verify's
+// flags, block i of stripe c iff gate[c*m + class of i] != 0.  The test is one
+// scalar byte read per tile; a tile that fails it reads nothing else.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool digest_wanted(const uint8_t* gate, int mode, uint64_t c,
+                                              uint64_t i, const Geometry& g) {
+  if (mode == kDigestAll) return true;
+  const uint64_t at = mode == kDigestSelect ? c * (g.k + g.m) + i
+                                            : c * g.m + (i < g.k ? i % g.m : i - g.k);
+  return sbyte(reinterpret_cast<uint64_t>(gate) + at) != 0;
+}
+
+// The two words of one granule; z = (n + 1) * golden of its first word.
+__device__ __forceinline__ uint64_t digest_granule(u32x4 v, uint64_t z) {
+  const uint64_t w0 = (uint64_t)v.x | ((uint64_t)v.y << 32);
+  const uint64_t w1 = (uint64_t)v.z | ((uint64_t)v.w << 32);
+  return splitmix_mix(w0 + z) + splitmix_mix(w1 + z + kSplitmixGolden);
+}
+
+// g.tiles_per_block = segments per block, g.total_tiles = S * (k+m) * that.
+template <bool NT, int T>
+__global__ __launch_bounds__(T) void digest_kernel(const uint8_t* __restrict__ data,
+                                                   const uint8_t* __restrict__ parity,
+                                                   const uint8_t* __restrict__ gate, int mode,
+                                                   uint64_t* out, Geometry g) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  constexpr uint64_t kStepZ = (uint64_t)(2 * T) * kSplitmixGolden;  // 2*T words per step
+  constexpr int kInFlight = 8;  // loads in flight per lane, as the generic reductions above
+  __shared__ uint64_t wave_sum[T / 64];
+  const uint64_t tot = g.k + g.m;
+  for (uint64_t t = blockIdx.x; t < g.total_tiles; t += gridDim.x) {
+    const uint64_t seg = t % g.tiles_per_block, b = t / g.tiles_per_block;
+    const uint64_t c = b / tot, i = b % tot;
+    if (!digest_wanted(gate, mode, c, i, g)) continue;  // uniform: scalar loads only
+    const uint8_t* blk = i < g.k ? data + (c * g.k + i) * g.bs
+                                 : parity + (c * g.m + (i - g.k)) * g.bs;
+    const uint64_t begin = seg * kDigestSegmentBytes;
+    const uint64_t end = g.bs - begin < kDigestSegmentBytes ? g.bs : begin + kDigestSegmentBytes;
+    uint64_t off = begin + threadIdx.x * 16ull;
+    uint64_t z = (off / 8 + 1) * kSplitmixGolden;  // (n + 1) * golden of this lane's first word
+    uint64_t acc = 0;
+    for (; off + (kInFlight - 1) * kStep < end; off += kInFlight * kStep, z += kInFlight * kStepZ) {
+      u32x4 v[kInFlight];
+#pragma unroll
+      for (int q = 0; q < kInFlight; ++q) v[q] = ld16<NT>(blk + off + q * kStep);
+#pragma unroll
+      for (int q = 0; q < kInFlight; ++q) acc += digest_granule(v[q], z + q * kStepZ);
+    }
+    // Fewer than kInFlight granules left (a 4 KiB block is nothing else): every
+    // load is issued before the first multiply here too.  With one load, then
+    // its multiplies, then the next, config 4 ran 10-13 % slower (1862-1953
+    // against 1696 us, profiles/digest/).
+    if (off < end) {
+      u32x4 v[kInFlight - 1];
+#pragma unroll
+      for (int q = 0; q < kInFlight - 1; ++q)
+        if (off + q * kStep < end) v[q] = ld16<NT>(blk + off + q * kStep);
+#pragma unroll
+      for (int q = 0; q < kInFlight - 1; ++q)
+        if (off + q * kStep < end) acc += digest_granule(v[q], z + q * kStepZ);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    if constexpr (T > 64) {  // the tile loop is uniform per workgroup: every wave gets here
+      if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = acc;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        acc = 0;
+#pragma unroll
+        for (int w = 0; w < T / 64; ++w) acc += wave_sum[w];
+      }
+      __syncthreads();  // wave_sum is free for the next tile
+    }
+    if (threadIdx.x == 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(out + b), (unsigned long long)acc);
+  }
+}
+
+// out[b] = 0 for every slot digest_kernel is going to add to (modes Select and
+// Flags; with every block wanted the caller uses a memset).  One thread per slot.
+__global__ __launch_bounds__(256) void digest_zero_kernel(const uint8_t* __restrict__ gate, int mode,
+                                                         uint64_t* out, Geometry g) {
+  const uint64_t tot = g.k + g.m, n = g.S * tot;
+  for (uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (uint64_t)gridDim.x * 256) {
+    const uint64_t c = b / tot, i = b % tot;
+    const uint64_t at = mode == kDigestSelect ? b : c * g.m + (i < g.k ? i % g.m : i - g.k);
+    if (gate[at] != 0) out[b] = 0;
+  }
+}
+
+// xec_locate's verdict: bitmap[b] = 0 where block b was checked (every block,
+// or gate = the flags of its class nonzero) and fresh[b] != stored[b], else 1;
+// *count += the zeros written (the caller zeroes it first), one atomicAdd per
+// wave that found any, as count_flags_kernel.  The grid-stride loop is uniform
+// per wave only up to n, so lanes past it carry 0 into the shuffle.
+__global__ __launch_bounds__(256) void locate_compare_kernel(const uint64_t* __restrict__ fresh,
+                                                            const uint64_t* __restrict__ stored,
+                                                            const uint8_t* __restrict__ gate,
+                                                            uint8_t* __restrict__ bitmap,
+                                                            uint32_t* count, Geometry g) {
+  const uint64_t tot = g.k + g.m, n = g.S * tot;
+  uint32_t mine = 0;
+  for (uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x; b < n; b += (uint64_t)gridDim.x * 256) {
+    const uint64_t c = b / tot, i = b % tot;
+    const bool checked = gate == nullptr || gate[c * g.m + (i < g.k ? i % g.m : i - g.k)] != 0;
+    const bool bad = checked && fresh[b] != stored[b];
+    bitmap[b] = bad ? 0 : 1;
+    mine += bad;
+  }
+  if (count == nullptr) return;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
+  if ((threadIdx.x & 63u) == 0 && mine != 0) atomicAdd(count, mine);
+}
+
+hipError_t launch_digest(const void* d_data, const void* d_parity, const uint8_t* d_gate, int mode,
+                         uint64_t* d_out, const Geometry& g_class, const LaunchShape& ls,
+                         hipStream_t s) {
+  Geometry g = g_class;
+  g.tiles_per_block = (g.bs + kDigestSegmentBytes - 1) / kDigestSegmentBytes;
+  g.total_tiles = g.S * (g.k + g.m) * g.tiles_per_block;
+  if (g.total_tiles == 0) return hipSuccess;
+  if (d_out == nullptr || (mode != kDigestAll && d_gate == nullptr) || mode < kDigestAll ||
+      mode > kDigestFlags)
+    return hipErrorInvalidValue;
+  const uint8_t* dd = static_cast<const uint8_t*>(d_data);
+  const uint8_t* pp = static_cast<const uint8_t*>(d_parity);
+  const uint64_t slots = g.S * (g.k + g.m);
+  hipError_t e = mode == kDigestAll
+                     ? hipMemsetAsync(d_out, 0, slots * sizeof(uint64_t), s)
+                     : launch(digest_zero_kernel, grid_for((slots + 255) / 256, 8192, 256), 256, 0,
+                              s, d_gate, mode, d_out, g);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt ? launch_codec(digest_kernel<true, 256>, grid, 256, lds, s, dd, pp, d_gate, mode,
+                                d_out, g)
+                 : launch_codec(digest_kernel<false, 256>, grid, 256, lds, s, dd, pp, d_gate, mode,
+                                d_out, g);
+  return ls.nt ? launch_codec(digest_kernel<true, 64>, grid, 64, lds, s, dd, pp, d_gate, mode,
+                              d_out, g)
+               : launch_codec(digest_kernel<false, 64>, grid, 64, lds, s, dd, pp, d_gate, mode,
+                              d_out, g);
+}
+
+hipError_t launch_locate_compare(const uint64_t* d_fresh, const uint64_t* d_stored,
+                                 const uint8_t* d_flags, uint8_t* d_bitmap, uint32_t* d_count,
+                                 const Geometry& g, hipStream_t s) {
+  const uint64_t slots = g.S * (g.k + g.m);
+  if (slots == 0) return hipSuccess;
+  return launch(locate_compare_kernel, grid_for((slots + 255) / 256, 1024, 256), 256, 0, s,
+                d_fresh, d_stored, d_flags, d_bitmap, d_count, g);
 }
 
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set

@@ -8,8 +8,8 @@ from ._lib import EXPORTED, LIB_PATH, Status, XecLibraryError, lib
 from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitmap, decode,
                     decode_arg_capacity_used, decode_device, decode_device_list,
                     decode_per_stripe, decode_tiling_used,
-                    device_list_bytes, encode, erase,
-                    fill_splitmix64, init, repair, repair_device, repair_tiling_used,
+                    device_list_bytes, digest, digest_host, encode, erase,
+                    fill_splitmix64, init, locate, locate_work_bytes, repair, repair_device, repair_tiling_used,
                     select_lost_blocks, set_decode_tiling, set_kernel_events, set_launch,
                     set_occupancy,
                     set_rotation, set_validate_kernel,
@@ -21,8 +21,9 @@ __all__ = [
     "DECODE_KERNELS", "EXPORTED", "LIB_PATH", "Pipeline", "Status", "XecLibraryError", "lib",
     "build_info", "check_args", "check_bitmap", "decode", "decode_arg_capacity_used",
     "decode_device", "decode_device_list",
-    "decode_per_stripe", "decode_tiling_used", "device_list_bytes",
-    "encode", "erase", "fill_splitmix64", "init", "repair", "repair_device",
+    "decode_per_stripe", "decode_tiling_used", "device_list_bytes", "digest", "digest_host",
+    "encode", "erase", "fill_splitmix64", "init", "locate", "locate_work_bytes", "repair",
+    "repair_device",
     "repair_tiling_used", "select_lost_blocks", "set_decode_tiling",
     "set_kernel_events",
     "set_launch",

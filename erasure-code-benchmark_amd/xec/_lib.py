@@ -32,6 +32,7 @@ EXPORTED = (
     "xec_decode_arg_capacity_used", "xec_peer_link", "xec_set_kernel_events",
     "xec_repair", "xec_repair_device", "xec_repair_tiling_used", "xec_verify",
     "xec_update", "xec_update_device", "xec_update_scratch_bytes", "xec_update_tiling_used",
+    "xec_digest_host", "xec_digest", "xec_locate", "xec_locate_work_bytes",
 )
 
 
@@ -118,6 +119,10 @@ def lib() -> ctypes.CDLL:
         "xec_update_device": ([vp, vp, vp, sz, sz, sz, sz, vp, vp], st),
         "xec_update_scratch_bytes": ([sz], sz),
         "xec_update_tiling_used": ([], ctypes.c_int),
+        "xec_digest_host": ([vp, sz], ctypes.c_uint64),
+        "xec_digest": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_locate_work_bytes": ([sz, sz, sz], sz),
+        "xec_locate": ([vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, sz, vp], st),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

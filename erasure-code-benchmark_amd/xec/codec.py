@@ -144,6 +144,44 @@ def update_tiling_used() -> int:
     return int(lib().xec_update_tiling_used())
 
 
+def digest_host(block) -> int:
+    """xec_digest_host -- the digest of one block in host memory (a C-contiguous
+    numpy array or bytes whose length is a multiple of 8): the sum over its
+    little-endian u64 words w[n] of splitmix_at(w[n], n), mod 2^64.  Host only."""
+    if isinstance(block, (bytes, bytearray)):
+        buf = (ctypes.c_char * len(block)).from_buffer_copy(block)
+        return int(lib().xec_digest_host(ctypes.addressof(buf), len(block)))
+    return int(lib().xec_digest_host(_ptr(block), block.nbytes))
+
+
+def digest(d_data, d_parity, S: int, bs: int, k: int, m: int, d_digests, d_select=None,
+           stream=None) -> Status:
+    """xec_digest -- d_digests (S*(k+m) device uint64, the bitmap's layout) =
+    the digest of every block, or with d_select (S*(k+m) device bytes, NONZERO =
+    digest this block) of the selected ones only; other slots are untouched."""
+    return Status(lib().xec_digest(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                   _ptr(d_select) if d_select is not None else None,
+                                   _ptr(d_digests), _stream(stream)))
+
+
+def locate_work_bytes(S: int, k: int, m: int) -> int:
+    """xec_locate_work_bytes: 8 * S * (k+m)."""
+    return int(lib().xec_locate_work_bytes(S, k, m))
+
+
+def locate(d_data, d_parity, S: int, bs: int, k: int, m: int, d_digests, d_flags, d_bitmap,
+           d_count, d_work, work_bytes: int, stream=None) -> Status:
+    """xec_locate -- d_bitmap (S*(k+m) device bytes) = 0 where a block's digest
+    differs from d_digests, else 1; d_flags None checks every block, else only
+    the classes xec_verify flagged; d_count (device uint32, optional) = the
+    zeros written.  d_bitmap is what repair_device takes."""
+    return Status(lib().xec_locate(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_digests),
+                                   _ptr(d_flags) if d_flags is not None else None,
+                                   _ptr(d_bitmap),
+                                   _ptr(d_count) if d_count is not None else None,
+                                   _ptr(d_work), work_bytes, _stream(stream)))
+
+
 def erase(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, stream=None) -> Status:
     """xec_erase -- device-side simulate_data_loss (abstract_bm.cpp:20-39)."""
     return Status(lib().xec_erase(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_bitmap),

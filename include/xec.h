@@ -235,7 +235,8 @@ int xec_repair_tiling_used(void);
  * copies between replays the captured scrub has been exact.
  * What it cannot tell: WHICH block of a flagged class is at fault (a class's
  * blocks enter the XOR alike), and two errors of one class that cancel -- the
- * same bits flipped at the same offset of two of its blocks -- are invisible. */
+ * same bits flipped at the same offset of two of its blocks -- are invisible.
+ * xec_locate with stored block digests (below) answers both. */
 xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                       size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream);
 
@@ -310,6 +311,92 @@ xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, si
  * xec_repair_tiling_used are not affected. */
 int xec_update_tiling_used(void);
 
+/* Block digests (no reference counterpart: its only checksum lives inside its
+ * validation payload).  XOR parity says THAT a class is damaged, never which
+ * of its blocks; a parity store keeps a small checksum per block for that.
+ * For a block of bs bytes read as bs/8 little-endian u64 words w[0..]:
+ *     digest(block) = sum over n of splitmix_at(w[n], n)      (mod 2^64)
+ * where splitmix_at(seed, n) is the splitmix64 finaliser of
+ * seed + (n+1)*0x9E3779B97F4A7C15 (output n of xec_fill_splitmix64's stream
+ * from state `seed`).
+ *  - Bit-exact under any reduction order: the sum is modulo 2^64, associative
+ *    and commutative, so the device's split over lanes, waves, workgroups and
+ *    atomic adds gives the host's bits.
+ *  - Detection: for fixed n the term is a bijection of w[n], so damage
+ *    confined to ONE 8-byte word always changes the digest; wider damage goes
+ *    unnoticed with probability about 2^-64.  Not cryptographic: it guards
+ *    against corruption, not against an adversary.
+ * xec_digest_host: host only, no GPU and no xec_init needed; bs % 8 == 0 (a
+ * tail of bs % 8 bytes is ignored). */
+uint64_t xec_digest_host(const void* block, size_t bs);
+
+/* Digests of a batch's blocks on the device.  d_digests: S*(k+m) u64 of device
+ * memory in the bitmap's layout -- stripe c at c*(k+m), its k data slots then
+ * its m parity slots.  d_select == NULL digests every block; otherwise it is
+ * S*(k+m) device bytes in the same layout and NONZERO means "digest this
+ * block" (the sense of xec_update_device's mask): the slot of an unselected
+ * block is neither read nor written, and the block itself is not read.  That
+ * is the refresh after xec_update: select the changed data blocks and the
+ * parity blocks of their classes, and the batch is not read again.
+ * Enqueues on `stream` (no host work: capturable; asynchronous): the selected
+ * slots zeroed (one memset when d_select is NULL, which a capture records as a
+ * memset node -- see xec_verify; else a small kernel), then one kernel over
+ * (block, 64 KiB segment) tiles, each adding its segment's sum to the block's
+ * slot with one 64-bit atomic add; at most 131,072 workgroups walk the tiles
+ * (xec_set_launch's max_grid overrides that; of its other arguments
+ * cache_policy and block_threads apply, unroll does not).  Reads up to (k+m)*bs*S bytes once, writes
+ * only d_digests.
+ * Checks, all on the host before anything is queued, in this order:
+ * XEC_NOT_INITIALIZED; xec_check_args; d_digests NULL with S > 0 ->
+ * XEC_INVALID_SIZE; d_digests not 8-byte aligned -> XEC_INVALID_ALIGNMENT.
+ * S == 0 is XEC_SUCCESS with nothing queued. */
+xec_status xec_digest(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, const uint8_t* d_select, uint64_t* d_digests, hipStream_t stream);
+
+/* Scratch bytes xec_locate needs: 8 * S * (k+m), one u64 per block. */
+size_t xec_locate_work_bytes(size_t S, size_t k, size_t m);
+
+/* Which block is damaged: recomputes digests into d_work (device scratch of at
+ * least xec_locate_work_bytes(S, k, m) bytes, 8-byte aligned), compares them
+ * with the stored d_digests and writes d_bitmap, S*(k+m) device bytes: 1 where
+ * the digest matches or the block was not checked, 0 where it differs -- the
+ * convention xec_repair_device and xec_erase read.  *d_count (device uint32,
+ * 4-byte aligned, or NULL) = the number of 0 bytes written.  Neither data nor
+ * parity is ever written.
+ * d_flags == NULL checks every block; that also finds what xec_verify cannot
+ * see, two errors of one class that cancel in the XOR.  Otherwise d_flags is
+ * xec_verify's S*m flag bytes, and only the k/m + 1 blocks of the classes with
+ * a nonzero flag are read and checked (a workgroup of an unflagged class
+ * returns after one byte read): the gate.  A block of an unflagged class
+ * reads 1 whatever its stored digest says.
+ * The chain xec_verify -> xec_locate(flags) -> xec_repair_device runs on one
+ * stream with no host step.  For a flagged class, one of:
+ *  - exactly one block differs: xec_repair_device rebuilds it from the others
+ *    and the class XORs to zero again;
+ *  - two or more blocks differ: *d_status = 4 and nothing is written (repair
+ *    is all-or-nothing over the batch);
+ *  - no block differs: the digests are stale, or the damage is older than
+ *    they are.  Nothing is repaired and the class stays flagged; *d_count
+ *    smaller than xec_verify's count of flagged classes tells the caller.
+ * Digests of rebuilt blocks need no refresh: a rebuilt block matches its
+ * stored digest again.
+ * Enqueues on `stream` (no host work: capturable on its own; asynchronous):
+ * *d_count zeroed by a memset; the checked slots of d_work zeroed (a memset
+ * with d_flags NULL, else a small kernel); the digest kernel of xec_digest;
+ * a small kernel that compares and counts.  A captured xec_locate therefore
+ * contains memset nodes, as a captured xec_verify does: the open observation
+ * recorded at xec_verify applies, and the chain is meant for a plain stream.
+ * Checks, all on the host before anything is queued, in this order:
+ * XEC_NOT_INITIALIZED; xec_check_args; d_digests or d_work NULL with S > 0, or
+ * work_bytes too small -> XEC_INVALID_SIZE; d_digests or d_work not 8-byte
+ * aligned, or d_count not 4-byte aligned -> XEC_INVALID_ALIGNMENT; d_bitmap
+ * NULL with S > 0 -> XEC_INVALID_SIZE.  S == 0 is XEC_SUCCESS, with
+ * *d_count = 0 when d_count is given. */
+xec_status xec_locate(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                      size_t m, const uint64_t* d_digests, const uint8_t* d_flags,
+                      uint8_t* d_bitmap, uint32_t* d_count, void* d_work, size_t work_bytes,
+                      hipStream_t stream);
+
 /* Host-only recoverability scan used by xec_decode (no GPU needed):
  * returns XEC_DECODE_FAILURE if some stripe is unrecoverable, else
  * XEC_SUCCESS and sets *needs_recovery to 1 iff some stripe needs recovery. */
@@ -378,8 +465,8 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * k/m at the default launch shape -- 1 at k/m = 32, 2 at 16, 4 at 4 and 8;
  * for other member counts none below 8, 4 below 20, 2 below 56, else 1;
  * none at 1 and 2.  The repair kernels take the same table;
- * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels run
- * uncapped at every k/m (their own sweep).  The reserved LDS keeps other kernels' LDS
+ * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels and
+ * the digest kernel run uncapped at every k/m (their own sweeps).  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
  * 0..8. */
 xec_status xec_set_occupancy(int waves_per_simd);
@@ -460,8 +547,9 @@ int xec_decode_arg_capacity_used(void);
 
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
- * xec_repair, xec_repair_device, xec_verify, xec_update or xec_update_device call
- * launches its encode / decode / repair / verify / update kernel with hipExtLaunchKernel and these two
+ * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
+ * xec_digest or xec_locate call
+ * launches its encode / decode / repair / verify / update / digest kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
  * time, with no event packet queued between kernels (a hipEventRecord between
