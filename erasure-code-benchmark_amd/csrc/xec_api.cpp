@@ -1413,6 +1413,154 @@ xec_status xec_locate(const void* d_data, const void* d_parity, size_t S, size_t
   return e == hipSuccess ? XEC_SUCCESS : DEVERR(e);
 }
 
+// ---- degraded read ----------------------------------------------------------------
+// xec_read / xec_read_device: bytes [offset, offset + len) of the blocks the
+// items name, packed into d_out; a lost block's range is reconstructed from
+// the same range of the other blocks of its class (xec_kernels.hip, degraded
+// read).  Nothing but d_out is written.  Always list tiles, one per (item,
+// chunk of the range).
+//
+// Residency (read_occupancy).  A reconstruct tile is one class reduction, as a
+// tile of encode or of the list decode, so it starts from their table
+// (auto_occupancy); a copy tile has one load in flight per lane, which a cap
+// only starves, so a list the host scan found free of losses runs uncapped.
+// The device form cannot know and takes the table.
+// Swept once, capped against uncapped, at configs 2, 3 and 4 (k/m = 8, 16, 32)
+// with one whole lost block per stripe and with the same blocks present
+// (tools/read_bench.py --sweep, profiles/read/; kernel times in us, cap 0 = this
+// function's choice):
+//   reconstruct  cap 0    1      2      4      8 (none)
+//     config 2   95.5   124.3  105.1   94.9   95.7      (the table's 4 = none)
+//     config 3   683.1  767.8  685.0  739.1  716.3      (the table's 2: 4.6 % ahead of none)
+//     config 4   1249   1248   1343   1309   1317       (the table's 1: 5.2 % ahead of none)
+//   copy
+//     config 2   21.9    78.1   46.9   30.2   21.9
+//     config 3   84.8   304.3  184.8  112.7   84.8
+//     config 4   163.8  372.4  224.3  163.9  163.7
+// so the table stands for reconstructions, and a copy wants every wave it can
+// get.  (Taken with d_out stored nt; the shipped sc1 store is 0.5-3 % faster
+// in each row, xec_kernels.hip.)
+static int read_occupancy(uint64_t nm, size_t n_lost) { return n_lost == 0 ? 0 : auto_occupancy(nm); }
+
+static thread_local int g_read_tiling_used = 0;  // xec_read_tiling_used: this thread's last read
+
+// The checks both forms share once the items' source is set aside, in
+// include/xec.h's order (steps 4 to 8; `items` is h_items or d_items).
+static xec_status read_check_range(const void* d_data, const void* d_parity, size_t S, size_t bs,
+                                   size_t k, size_t m, const void* items, size_t n, size_t offset,
+                                   size_t len, const void* d_out) {
+  if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset > bs || len > bs - offset)
+    return XEC_INVALID_SIZE;
+  if (d_out == nullptr || items == nullptr) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return XEC_INVALID_ALIGNMENT;
+  if (n > SIZE_MAX / len || ranges_overlap(d_out, n * len, d_data, S * k * bs) ||
+      ranges_overlap(d_out, n * len, d_parity, S * m * bs))
+    return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+static xec_status read_impl(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                            size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n,
+                            size_t offset, size_t len, void* d_out, void* d_scratch,
+                            size_t scratch_bytes, hipStream_t stream) {
+  g_read_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (n == 0 || S == 0) return XEC_SUCCESS;
+  st = read_check_range(d_data, d_parity, S, bs, k, m, h_items, n, offset, len, d_out);
+  if (st != XEC_SUCCESS) return st;
+  const bool in_args = n <= xec::kArgItems;
+  uint32_t short_bits[xec::kArgItems / 32];
+  size_t n_lost = 0;
+  st = xec_scan_read_items(h_bitmap, S, k, m, h_items, n, in_args ? short_bits : nullptr, &n_lost);
+  if (st != XEC_SUCCESS) return st;
+  if (!in_args) {
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+    if (d_scratch == nullptr || scratch_bytes < xec_read_scratch_bytes(n)) return XEC_INVALID_SIZE;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, n_lost));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_read_tiling_used = XEC_TILING_ARG_LIST;
+    const hipError_t le =
+        xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadArgListTiles, offset, len, n,
+                         nullptr, nullptr, h_items, short_bits, stream);
+    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  }
+  // items, then their loss bits, staged in pinned memory and uploaded on
+  // `stream` itself in one copy, as xec_update uploads its list
+  const StreamDevice sd(stream);
+  if (!sd.ok()) return DEVERR(hipSuccess);
+  bool fault = false;
+  const size_t bytes = xec_read_scratch_bytes(n);
+  Staging* sg = stage_acquire(bytes, sd.device(), &fault);
+  if (sg == nullptr) return DEVERR(hipSuccess);
+  uint32_t* staged = static_cast<uint32_t*>(sg->host);
+  std::memcpy(staged, h_items, n * 4);
+  (void)xec_scan_read_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr);
+  g_read_tiling_used = XEC_TILING_LIST;
+  hipError_t le = hipMemcpyAsync(d_scratch, staged, bytes, hipMemcpyHostToDevice, stream);
+  const bool queued = le == hipSuccess;
+  if (queued)
+    le = xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadListTiles, offset, len, n,
+                          static_cast<const uint32_t*>(d_scratch), nullptr, nullptr, nullptr,
+                          stream);
+  stage_release(sg, queued, stream, false);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
+xec_status xec_read(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                    size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n_items,
+                    size_t offset, size_t len, void* d_out, void* d_scratch, size_t scratch_bytes,
+                    hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  try {  // as xec_decode
+    return read_impl(d_data, d_parity, S, bs, k, m, h_bitmap, h_items, n_items, offset, len, d_out,
+                     d_scratch, scratch_bytes, stream);
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+size_t xec_read_scratch_bytes(size_t n_items) { return 4 * xec::read_list_words(n_items); }
+
+int xec_read_tiling_used(void) { return g_read_tiling_used; }
+
+xec_status xec_read_device(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                           size_t m, const uint8_t* d_bitmap, const uint32_t* d_items,
+                           size_t n_items, size_t offset, size_t len, void* d_out,
+                           int32_t* d_status, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_read_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (n_items != 0 && S != 0) {
+    st = read_check_range(d_data, d_parity, S, bs, k, m, d_items, n_items, offset, len, d_out);
+    if (st != XEC_SUCCESS) return st;
+    if (reinterpret_cast<uintptr_t>(d_items) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+  }
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  if (n_items == 0 || S == 0) return XEC_SUCCESS;
+  // No host view of the bitmap: the table of a reconstruct tile (read_occupancy).
+  const xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, d_bitmap ? 1 : 0));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_read_check(d_bitmap, d_items, n_items, g, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  g_read_tiling_used = XEC_TILING_LIST;
+  const hipError_t le =
+      xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadDevTiles, offset, len, n_items,
+                       d_items, d_bitmap, nullptr, nullptr, stream);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
   if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;

@@ -59,6 +59,20 @@ constexpr size_t kRepairItemMaxRow = 256;
 xec_status xec_scan_repair(const uint8_t* h_bitmap, size_t S, size_t k, size_t m, uint32_t* items,
                            uint64_t cap, uint64_t* n_items);
 
+// Read scan (xec_read; xec_check_read_items is this with lost_bits null): the
+// verdict over the n_items REQUESTED items c << 8 | i, i in [0, k+m).  An item
+// is servable if its block is present (byte != 0, or bm null), or lost with
+// every other block of its class present; other classes and stripes play no
+// part.  XEC_INVALID_COUNTS if any item has c >= S or i >= k + m (or k, m as
+// xec_check_args, or items null with n_items > 0), else XEC_DECODE_FAILURE if
+// any is not servable.  On success *n_lost (may be null) = the items that need
+// a reconstruction (a repeated item counts each time) and, when lost_bits is
+// non-null, bit t of word t / 32 of its (n_items + 31) / 32 words = item t is
+// lost.  Defined in xec_scan.cpp.
+xec_status xec_scan_read_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                               const uint32_t* items, size_t n_items, uint32_t* lost_bits,
+                               size_t* n_lost);
+
 // masks[c] = bit i set iff data byte i of stripe c's row is 0 (lost), for the
 // kernel-argument mask decode (xec_kernels.hip decode_argmask_kernel).
 // Requires k <= 32; the rows must already have passed xec_scan_bitmap (no

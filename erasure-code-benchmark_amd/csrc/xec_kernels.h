@@ -109,7 +109,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
 }
 
 // The codec kernels (encode, every decode, repair and update tiling, verify,
-// digest) go through this: as launch(), but with the thread's pending kernel events,
+// digest, read) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -226,6 +226,36 @@ hipError_t launch_digest(const void* d_data, const void* d_parity, const uint8_t
 hipError_t launch_locate_compare(const uint64_t* d_fresh, const uint64_t* d_stored,
                                  const uint8_t* d_flags, uint8_t* d_bitmap, uint32_t* d_count,
                                  const Geometry& g, hipStream_t s);
+// Degraded read (xec_read, xec_read_device): bytes [offset, offset + len) of
+// the block each item names (c << 8 | i, i in [0, k+m), i >= k parity block
+// i - k; any order, repeats allowed) go to d_out + t*len for the t-th item.  A
+// tile is (item, chunk of the RANGE), chunks of 16*threads*unroll bytes; a
+// present block's tile copies, a lost block's tile runs its class's reduction
+// over the same range of the other k/m blocks straight into d_out.  Nothing
+// but d_out is written, and a lost block is never read.  offset, len % 16 == 0,
+// offset + len <= bs, k + m <= 256.  Of g only S, k, m, nm, bs and gate are
+// used (the tile counts are the range's, and there is no column rotation: an
+// item's chunks are one short run, not a walk down every stripe's column).
+// Where the verdict (copy or reconstruct) comes from:
+//   kReadArgListTiles  h_items and h_lost (bit t of word t / 32 = item t is
+//                      lost) by value in the kernel arguments, n <= kArgItems;
+//   kReadListTiles     d_items = n u32 items followed by (n + 31) / 32 u32 words
+//                      of the same bits (read_list_words(n) words in all);
+//   kReadDevTiles      d_items = n u32 items, d_bitmap = the batch bitmap (byte
+//                      0 = lost) or nullptr (everything present); g.gate set.
+constexpr int kReadListTiles = 0;
+constexpr int kReadArgListTiles = 1;
+constexpr int kReadDevTiles = 2;
+inline uint64_t read_list_words(uint64_t n) { return n + (n + 31) / 32; }
+hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out, const Geometry& g,
+                       const LaunchShape& ls, int tiling, uint64_t offset, uint64_t len,
+                       uint64_t n_items, const uint32_t* d_items, const uint8_t* d_bitmap,
+                       const uint32_t* h_items, const uint32_t* h_lost, hipStream_t s);
+// xec_read_device's verdict: *d_status = max over the n items of 0 (servable),
+// 3 (c >= S or i >= k + m; never dereferenced) and 4 (lost, and another block
+// of its class lost too).  The caller zeroes *d_status first, stream-ordered.
+hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
+                             const Geometry& g, int32_t* d_status, hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

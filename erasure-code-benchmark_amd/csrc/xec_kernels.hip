@@ -1419,6 +1419,347 @@ hipError_t launch_locate_compare(const uint64_t* d_fresh, const uint64_t* d_stor
                 d_fresh, d_stored, d_flags, d_bitmap, d_count, g);
 }
 
+// ---------------------------------------------------------------------------
+// degraded read (xec_read, xec_read_device).  Kernels and launchers together,
+// after every older one, so the older kernels keep their place.
+//
+// Item e = c << 8 | i (repair's packing) asks for bytes [offset, offset + len)
+// of block i of stripe c, delivered at out + e*len.  A tile is (item, chunk of
+// the RANGE): chunk q covers block offsets offset + q*16*T*U onwards, and
+// g.tiles_per_block counts the chunks of the range, not of the block.  The
+// item and its verdict -- copy, or reconstruct -- are scalar loads (kernel
+// arguments, the uploaded list, or the device bitmap), so the branch is
+// uniform per workgroup:
+//   present: one 16-byte load and one store per granule;
+//   lost:    the reduction of its class over the same range of the other k/m
+//            blocks (decode's for a data block, encode's for a parity block;
+//            xor_members_to, every member's loads in flight), whose result
+//            goes straight to out.  The lost block itself is never read.
+// data, parity and the bitmap are only read.
+//
+// Bounds.  The range starts and ends inside the block, so neither end is the
+// block's.  Lower: a lane's first granule is offset + (q*T*U + lane)*16, never
+// below offset, and the store address is formed from the item's own output
+// base, out + e*len, plus the granule's distance from `offset` -- no pointer
+// below out is ever formed.  Upper: xor_members_to takes offset + len as the
+// end of what the tile may touch (its ragged-tail predicate), the copy path
+// tests the same bound, and the NT store's buffer resource is `len` bytes long,
+// so the hardware drops anything past the item's slot as well.
+//
+// Store policy of out (kReadStoreAux; buffer aux bits as above): sc1.  Decode's
+// sc1 was chosen because the rebuilt line shares an L2 set with the blocks read
+// in place; out is a separate buffer, so that argument does not carry over and
+// the three policies were measured: libraries built from one tree with
+// -DXEC_READ_STORE_AUX=2 / 16 / 0, tools/read_bench.py on each in turn, twice
+// over (kernel times in us, both passes; profiles/read/store_aux*.json):
+//   whole lost blocks, one per stripe   nt            sc1           default
+//     config 2                          89.7 / 91.3   89.2 / 88.7   91.5 / 91.4
+//     config 3                          681.1 / 670.5 661.6 / 650.8 683.6 / 666.7
+//     config 4                          1301 / 1302   1267 / 1269   1340 / 1344
+//   gather of the same blocks, present
+//     config 2                          22.8 / 22.4   20.8 / 21.1   23.6 / 23.8
+//     config 3                          85.4 / 85.4   76.7 / 76.6   80.5 / 79.3
+//     config 4                          164.0 / 164.8 158.8 / 159.3 158.8 / 158.4
+//   1,024 x 4 KiB of lost 1 MiB blocks  14.2 / 14.1   13.6 / 13.5   14.3 / 14.4
+// sc1 is the fastest or tied in every row of both passes (2.7-3 % ahead of nt
+// on reconstructions at configs 3 and 4, 6-10 % on the gather at 2 and 3): a
+// line of out is written once and not read by this kernel, and sc1 does not
+// keep it in the XCD's L2 beside the blocks still being read.
+// ---------------------------------------------------------------------------
+#ifndef XEC_READ_STORE_AUX
+#define XEC_READ_STORE_AUX 16  // sc1
+#endif
+constexpr int kReadStoreAux = XEC_READ_STORE_AUX;
+
+// xor_members (top of this file) with the store left to the caller:
+// store(o, v) takes the result of the granule at block offset o, and `end` is
+// the end of what the tile may touch -- here the range's end inside the block,
+// which plays the part the block's size plays there (the ragged-tail
+// predicate).  A copy and not a wrapper under xor_members: with xor_members
+// forwarding to this, 82 to 374 of the existing encode / decode / repair
+// kernels came out with other register assignments, and those kernels stay
+// instruction for instruction what they were.
+template <int NM, int U, bool NT, int T, typename Store>
+__device__ __forceinline__ void xor_members_to(const uint8_t* base, uint64_t stride,
+                                               const uint8_t* sub, int subst, uint64_t off,
+                                               uint64_t end, uint32_t nm_rt, Store store) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  if constexpr (NM > 0) {
+    if (off + (U - 1) * kStep < end) {  // whole tile inside the range: no predication
+      u32x4 v[NM][U];
+      const uint8_t* p = base + off;
+      const uint8_t* ps = sub + off;
+#pragma unroll
+      for (int r = 0; r < NM; ++r, p += stride) {
+        const uint8_t* src = r == subst ? ps : p;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = ld16<NT>(src + u * kStep);
+      }
+      if constexpr (NM >= 32) __builtin_amdgcn_sched_barrier(0);  // as xor_members
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u32x4 acc = v[0][u];
+#pragma unroll
+        for (int r = 1; r < NM; ++r) acc ^= v[r][u];
+        store(off + u * kStep, acc);
+      }
+      return;
+    }
+  }
+  // Ragged tail of the range, or a member count without a compiled unroll
+  // (groups of 8 loads in flight per granule).
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : nm_rt;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t o = off + u * kStep;
+    if (o >= end) continue;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    uint32_t r = 0;
+    for (; r + 8 <= nm; r += 8) {
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int rr = (int)(r + q);
+        v[q] = ld16<NT>((rr == subst ? sub : base + (uint64_t)rr * stride) + o);
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc ^= v[q];
+    }
+    for (; r < nm; ++r) acc ^= ld16<NT>(((int)r == subst ? sub : base + (uint64_t)r * stride) + o);
+    store(o, acc);
+  }
+}
+
+struct ReadRange {
+  uint64_t offset, len;  // bytes, multiples of 16; offset + len <= bs
+};
+
+// 16 bytes at `rel` of the len-byte slot at `slot`.
+template <bool NT>
+__device__ __forceinline__ void st16_slot(uint8_t* slot, uint32_t len, uint64_t rel, u32x4 v) {
+  if constexpr (NT) {
+    const __amdgpu_buffer_rsrc_t rs =
+        __builtin_amdgcn_make_buffer_rsrc(slot, 0, (int)len, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (uint32_t)rel, 0, kReadStoreAux);
+  } else {
+    st16<false>(slot + rel, v);
+  }
+}
+
+template <int NM, int U, bool NT, int T>
+__device__ __forceinline__ void read_tile(const uint8_t* __restrict__ data,
+                                          const uint8_t* __restrict__ parity, uint8_t* out,
+                                          uint64_t e, uint32_t item, bool lost, uint64_t chunk,
+                                          const ReadRange& rr, const Geometry& g) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint32_t m = (uint32_t)g.m, k = (uint32_t)g.k;
+  const uint64_t c = item >> 8;
+  const uint32_t i = item & 0xFFu;
+  const uint64_t end = rr.offset + rr.len;
+  const uint64_t off = rr.offset + (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+  uint8_t* slot = out + e * rr.len;
+  const uint32_t len = (uint32_t)rr.len;
+  auto store = [&](uint64_t o, u32x4 v) { st16_slot<NT>(slot, len, o - rr.offset, v); };
+  if (!lost) {
+    const uint8_t* blk = i < k ? data + (c * g.k + i) * g.bs : parity + (c * g.m + (i - k)) * g.bs;
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (off + u * kStep < end) v[u] = ld16<NT>(blk + off + u * kStep);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (off + u * kStep < end) store(off + u * kStep, v[u]);
+    return;
+  }
+  const uint32_t j = i < k ? i % m : i - k;  // the item's class
+  const uint8_t* base = data + (c * g.k + j) * g.bs;
+  if (i < k)  // a data block: the other members and the class parity, as decode
+    xor_members_to<NM, U, NT, T>(base, g.m * g.bs, parity + (c * g.m + j) * g.bs, (int)(i / m), off,
+                                 end, nm, store);
+  else  // a parity block: every data member, as encode
+    xor_members_to<NM, U, NT, T>(base, g.m * g.bs, nullptr, -1, off, end, nm, store);
+}
+
+// Bit e of the loss bits that travel with a host-checked list.
+template <typename Word>
+__device__ __forceinline__ bool read_lost_bit(Word word_at, uint64_t e) {
+  return ((word_at(e >> 5) >> (uint32_t)(e & 31u)) & 1u) != 0;
+}
+
+// The list in device memory: n items, then the loss bits (xec_kernels.h).
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void read_list_kernel(const uint8_t* __restrict__ data,
+                                                      const uint8_t* __restrict__ parity,
+                                                      uint8_t* out,
+                                                      const uint32_t* __restrict__ items,
+                                                      ReadRange rr, Geometry g) {
+  const uint32_t* bits = items + g.total_tiles / g.tiles_per_block;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as decode_list_kernel
+    const uint64_t e = t / g.tiles_per_block;
+    const bool lost = read_lost_bit([&](uint64_t w) { return *(const_u32_as4)(bits + w); }, e);
+    read_tile<NM, U, NT, T>(data, parity, out, e, *(const_u32_as4)(items + e), lost,
+                            t % g.tiles_per_block, rr, g);
+  }
+}
+
+// The same with items and bits in the kernel arguments (at most CAP items).
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void read_arglist_kernel(const uint8_t* __restrict__ data,
+                                                         const uint8_t* __restrict__ parity,
+                                                         uint8_t* out, ReadRange rr, Geometry g,
+                                                         ArgItems<CAP> items,
+                                                         ArgItems<CAP / 32> bits) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    const uint64_t e = t / g.tiles_per_block;
+    const bool lost = read_lost_bit([&](uint64_t w) { return bits.v[w]; }, e);
+    read_tile<NM, U, NT, T>(data, parity, out, e, items.v[e], lost, t % g.tiles_per_block, rr, g);
+  }
+}
+
+// Items and bitmap on the device (xec_read_device; gated on read_check_kernel's
+// verdict, so every item it sees is in range and servable): the verdict is the
+// item's own bitmap byte, one scalar dword load.
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void read_dev_kernel(const uint8_t* __restrict__ data,
+                                                     const uint8_t* __restrict__ parity,
+                                                     uint8_t* out,
+                                                     const uint32_t* __restrict__ items,
+                                                     const uint8_t* __restrict__ bitmap,
+                                                     ReadRange rr, Geometry g) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    const uint64_t e = t / g.tiles_per_block;
+    const uint32_t item = *(const_u32_as4)(items + e);
+    const bool lost =
+        bitmap != nullptr && sbyte(reinterpret_cast<uint64_t>(bitmap) +
+                                   (uint64_t)(item >> 8) * (g.k + g.m) + (item & 0xFFu)) == 0;
+    read_tile<NM, U, NT, T>(data, parity, out, e, item, lost, t % g.tiles_per_block, rr, g);
+  }
+}
+
+// One thread per item: *status = max(*status, verdict), verdict 0 servable,
+// 3 out of range (nothing of it is dereferenced), 4 lost with another block of
+// its class lost too.  Only blocks of the item's own class are looked at.
+__global__ __launch_bounds__(256) void read_check_kernel(const uint8_t* __restrict__ bitmap,
+                                                        const uint32_t* __restrict__ items,
+                                                        uint64_t n, Geometry g, int32_t* status) {
+  const uint64_t row = g.k + g.m;
+  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n;
+       t += (uint64_t)gridDim.x * 256) {
+    const uint32_t item = items[t];
+    const uint64_t c = item >> 8, i = item & 0xFFu;
+    if (c >= g.S || i >= row) {
+      atomicMax(status, 3 /* XEC_INVALID_COUNTS */);
+      continue;
+    }
+    if (bitmap == nullptr) continue;
+    const uint8_t* r = bitmap + c * row;
+    if (r[i] != 0) continue;
+    const uint64_t j = i < g.k ? i % g.m : i - g.k;
+    uint32_t others = i < g.k ? r[g.k + j] == 0 : 0;
+    for (uint64_t l = j; l < g.k; l += g.m) others += l != i && r[l] == 0;
+    if (others != 0) atomicMax(status, 4 /* XEC_DECODE_FAILURE */);
+  }
+}
+
+namespace {
+
+template <int NM, int U, bool NT, int T>
+hipError_t launch_read_t(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g,
+                         int tiling, const ReadRange& rr, const uint32_t* d_items,
+                         const uint8_t* bm, const ArgList& al, const uint32_t* h_lost,
+                         uint32_t grid, uint32_t lds, hipStream_t s) {
+  if (tiling == kReadArgListTiles) {
+    switch (arg_items_capacity(al.n)) {
+      case 64:
+        return launch_codec(read_arglist_kernel<NM, U, NT, T, 64>, grid, T, lds, s, d, p, out, rr,
+                            g, arg_items<64>(al.items, al.n),
+                            arg_items<2>(h_lost, (al.n + 31) / 32));
+      case 256:
+        return launch_codec(read_arglist_kernel<NM, U, NT, T, 256>, grid, T, lds, s, d, p, out,
+                            rr, g, arg_items<256>(al.items, al.n),
+                            arg_items<8>(h_lost, (al.n + 31) / 32));
+      default:
+        return launch_codec(read_arglist_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, d, p, out,
+                            rr, g, arg_items<1024>(al.items, al.n),
+                            arg_items<32>(h_lost, (al.n + 31) / 32));
+    }
+  }
+  if (tiling == kReadListTiles)
+    return launch_codec(read_list_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items, rr, g);
+  return launch_codec(read_dev_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items, bm, rr,
+                      g);
+}
+
+template <int U, bool NT, int T>
+hipError_t read_nm(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g, int tiling,
+                   const ReadRange& rr, const uint32_t* d_items, const uint8_t* bm,
+                   const ArgList& al, const uint32_t* h_lost, uint32_t grid, uint32_t lds,
+                   hipStream_t s) {
+  XEC_NM_SWITCH(g.nm, return (launch_read_t<NM, U, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al,
+                                                          h_lost, grid, lds, s)))
+}
+
+template <bool NT, int T>
+hipError_t read_u(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g, int tiling,
+                  int unroll, const ReadRange& rr, const uint32_t* d_items, const uint8_t* bm,
+                  const ArgList& al, const uint32_t* h_lost, uint32_t grid, uint32_t lds,
+                  hipStream_t s) {
+  return unroll == 2
+             ? read_nm<2, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al, h_lost, grid, lds, s)
+             : read_nm<1, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al, h_lost, grid, lds, s);
+}
+
+}  // namespace
+
+hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out,
+                       const Geometry& g_class, const LaunchShape& ls, int tiling, uint64_t offset,
+                       uint64_t len, uint64_t n_items, const uint32_t* d_items,
+                       const uint8_t* d_bitmap, const uint32_t* h_items, const uint32_t* h_lost,
+                       hipStream_t s) {
+  if (n_items == 0) return hipSuccess;
+  if (d_out == nullptr || len == 0 || offset % 16 != 0 || len % 16 != 0 ||
+      offset + len > g_class.bs || g_class.k + g_class.m > 256 || tiling < kReadListTiles ||
+      tiling > kReadDevTiles)
+    return hipErrorInvalidValue;
+  if (tiling == kReadArgListTiles ? (n_items > kArgItems || h_items == nullptr || h_lost == nullptr)
+                                  : d_items == nullptr)
+    return hipErrorInvalidValue;
+  if (tiling == kReadDevTiles && g_class.gate == nullptr) return hipErrorInvalidValue;
+  Geometry g = g_class;
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
+  g.total_tiles = n_items * g.tiles_per_block;
+  g.rot = 0;
+  const ReadRange rr{offset, len};
+  const ArgList a{h_items, n_items};
+  const uint8_t* d = static_cast<const uint8_t*>(d_data);
+  const uint8_t* p = static_cast<const uint8_t*>(d_parity);
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt ? read_u<true, 256>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
+                                     h_lost, grid, lds, s)
+                 : read_u<false, 256>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
+                                      h_lost, grid, lds, s);
+  return ls.nt ? read_u<true, 64>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a, h_lost,
+                                  grid, lds, s)
+               : read_u<false, 64>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
+                                   h_lost, grid, lds, s);
+}
+
+hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
+                             const Geometry& g, int32_t* d_status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  return launch(read_check_kernel, grid_for((n + 255) / 256, 8192, 256), 256, 0, s, d_bitmap,
+                d_items, n, g, d_status);
+}
+
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set
 // is told once, on stderr, that every launch of the library will fail
 // (a silent hook in the shipped library).

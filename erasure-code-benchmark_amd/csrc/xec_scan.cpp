@@ -392,6 +392,48 @@ xec_status xec_scan_repair(const uint8_t* bm, size_t S, size_t k, size_t m, uint
   return XEC_SUCCESS;
 }
 
+// ---- read scan (xec_read, xec_check_read_items) --------------------------------
+// Per requested item, not per batch: a present item costs one byte read, a lost
+// one the k/m bytes of its class.  An out-of-range item anywhere in the list
+// outranks an unservable one, so the walk goes on after the first failure.
+xec_status xec_scan_read_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                               const uint32_t* items, size_t n_items, uint32_t* lost_bits,
+                               size_t* n_lost) {
+  if (n_lost) *n_lost = 0;
+  if (k < 1 || m < 1 || k % m != 0) return XEC_INVALID_COUNTS;
+  if (items == nullptr && n_items != 0) return XEC_INVALID_COUNTS;
+  const size_t row = k + m;
+  if (lost_bits != nullptr)
+    for (size_t w = 0; w < (n_items + 31) / 32; ++w) lost_bits[w] = 0;
+  size_t lost = 0;
+  bool failed = false;
+  for (size_t t = 0; t < n_items; ++t) {
+    const size_t c = items[t] >> 8, i = items[t] & 0xFFu;
+    if (c >= S || i >= row) return XEC_INVALID_COUNTS;
+    if (bm == nullptr || failed) continue;  // after a failure only the ranges matter
+    const uint8_t* r = bm + c * row;
+    if (r[i] != 0) continue;
+    const size_t j = i < k ? i % m : i - k;
+    bool alone = i >= k || r[k + j] != 0;
+    for (size_t l = j; l < k && alone; l += m) alone = l == i || r[l] != 0;
+    if (!alone) {
+      failed = true;
+      continue;
+    }
+    ++lost;
+    if (lost_bits != nullptr) lost_bits[t >> 5] |= 1u << (t & 31);
+  }
+  if (failed) return XEC_DECODE_FAILURE;
+  if (n_lost) *n_lost = lost;
+  return XEC_SUCCESS;
+}
+
+extern "C" xec_status xec_check_read_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                                           const uint32_t* items, size_t n_items,
+                                           size_t* n_lost) {
+  return xec_scan_read_items(bm, S, k, m, items, n_items, nullptr, n_lost);
+}
+
 namespace {
 
 void loss_masks_scalar(const uint8_t* bm, size_t S, size_t k, size_t m, uint32_t* masks) {

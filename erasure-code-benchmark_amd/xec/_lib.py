@@ -33,6 +33,8 @@ EXPORTED = (
     "xec_repair", "xec_repair_device", "xec_repair_tiling_used", "xec_verify",
     "xec_update", "xec_update_device", "xec_update_scratch_bytes", "xec_update_tiling_used",
     "xec_digest_host", "xec_digest", "xec_locate", "xec_locate_work_bytes",
+    "xec_read", "xec_read_scratch_bytes", "xec_read_device", "xec_check_read_items",
+    "xec_read_tiling_used",
 )
 
 
@@ -123,6 +125,11 @@ def lib() -> ctypes.CDLL:
         "xec_digest": ([vp, vp, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_locate_work_bytes": ([sz, sz, sz], sz),
         "xec_locate": ([vp, vp, sz, sz, sz, sz, vp, vp, vp, vp, vp, sz, vp], st),
+        "xec_read": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, sz, vp], st),
+        "xec_read_scratch_bytes": ([sz], sz),
+        "xec_read_device": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp], st),
+        "xec_check_read_items": ([vp, sz, sz, sz, vp, sz, ctypes.POINTER(sz)], st),
+        "xec_read_tiling_used": ([], ctypes.c_int),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

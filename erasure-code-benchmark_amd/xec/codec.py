@@ -182,6 +182,56 @@ def locate(d_data, d_parity, S: int, bs: int, k: int, m: int, d_digests, d_flags
                                    _ptr(d_work), work_bytes, _stream(stream)))
 
 
+def read(d_data, d_parity, S: int, bs: int, k: int, m: int, h_bitmap, h_items, n_items: int,
+         offset: int, length: int, d_out, d_scratch=None, scratch_bytes: int = 0,
+         stream=None) -> Status:
+    """xec_read -- bytes [offset, offset + length) of the block each of the n_items
+    host items c << 8 | i names (uint32; i >= k: parity block i - k; any order,
+    repeats allowed) go to d_out + t*length; a lost block (h_bitmap byte 0;
+    h_bitmap None = all present) is reconstructed from the rest of its class.
+    Nothing but d_out is written.  d_scratch (read_scratch_bytes(n_items) device
+    bytes) is needed only past 1,024 items."""
+    return Status(lib().xec_read(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                 _ptr(h_bitmap) if h_bitmap is not None else None,
+                                 _ptr(h_items) if h_items is not None else None, n_items,
+                                 offset, length, _ptr(d_out), _ptr(d_scratch), scratch_bytes,
+                                 _stream(stream)))
+
+
+def read_device(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, d_items,
+                n_items: int, offset: int, length: int, d_out, d_status, stream=None) -> Status:
+    """xec_read_device -- the same with bitmap (None = all present) and items on
+    the device; the verdict lands in d_status (int32 device tensor: 0, 3 an item
+    out of range, 4 an item not servable) in stream order; capturable."""
+    return Status(lib().xec_read_device(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                        _ptr(d_bitmap) if d_bitmap is not None else None,
+                                        _ptr(d_items) if d_items is not None else None, n_items,
+                                        offset, length, _ptr(d_out), _ptr(d_status),
+                                        _stream(stream)))
+
+
+def read_scratch_bytes(n_items: int) -> int:
+    """xec_read_scratch_bytes: 4 * (n_items + ceil(n_items / 32))."""
+    return int(lib().xec_read_scratch_bytes(n_items))
+
+
+def check_read_items(h_bitmap, S: int, k: int, m: int, h_items, n_items: int) -> tuple[Status, int]:
+    """xec_check_read_items -- the host scan xec_read runs (no GPU, no init):
+    (status, items that need a reconstruction)."""
+    n_lost = ctypes.c_size_t(0)
+    st = Status(lib().xec_check_read_items(_ptr(h_bitmap) if h_bitmap is not None else None,
+                                           S, k, m,
+                                           _ptr(h_items) if h_items is not None else None,
+                                           n_items, ctypes.byref(n_lost)))
+    return st, int(n_lost.value)
+
+
+def read_tiling_used() -> int:
+    """xec_read_tiling_used: the tiling this thread's last read launched (0 none,
+    3 list on the device, 4 list in the kernel arguments)."""
+    return int(lib().xec_read_tiling_used())
+
+
 def erase(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, stream=None) -> Status:
     """xec_erase -- device-side simulate_data_loss (abstract_bm.cpp:20-39)."""
     return Status(lib().xec_erase(_ptr(d_data), _ptr(d_parity), S, bs, k, m, _ptr(d_bitmap),

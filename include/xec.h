@@ -397,6 +397,101 @@ xec_status xec_locate(const void* d_data, const void* d_parity, size_t S, size_t
                       uint8_t* d_bitmap, uint32_t* d_count, void* d_work, size_t work_bytes,
                       hipStream_t stream);
 
+/* Degraded read (no reference counterpart: its decode rebuilds whole blocks in
+ * place): serve a read while a block is missing.  Item t names block i of
+ * stripe c as h_items[t] = c << 8 | i, xec_repair's packing -- i in [0, k+m),
+ * i >= k naming parity block i - k -- and bytes [offset, offset + len) of that
+ * block arrive at d_out + t*len.  A present block is copied.  A lost block's
+ * range is reconstructed from the same range of the other k/m blocks of its
+ * class, straight into d_out: k/m * len bytes read and len written, where
+ * xec_repair reads k/m * bs and writes bs, in place.  d_data, d_parity and the
+ * bitmap are never written, so a reader needs no write access to the store;
+ * the bytes a lost block holds on entry are never read.
+ * Items may come in any order and may repeat (a read has no writer conflict).
+ * A block is lost iff its bitmap byte is 0, xec_repair's rule; h_bitmap == NULL
+ * means everything is present and the call is a pure gather.  An item is
+ * servable if its block is present, or if it is lost and every other block of
+ * its class is present (the k/m - 1 other data members and the parity block;
+ * all k/m data members when the item is the parity block).
+ * Unlike xec_repair, blocks of other classes and other stripes play no part:
+ * a batch xec_repair refuses (XEC_DECODE_FAILURE, some class lost two blocks)
+ * still serves every read that does not ask for a LOST block of such a class
+ * -- its present blocks included.  All-or-nothing over the REQUESTED items: if
+ * one is not servable nothing is written to d_out.
+ * Checks, all on the host before any device call, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. xec_check_args;
+ *  3. n_items == 0 or S == 0 -> XEC_SUCCESS, nothing queued;
+ *  4. k + m > 256 or S > 2^24 -> XEC_INVALID_SIZE (the packing);
+ *  5. len == 0, offset % 16, len % 16 or offset + len > bs -> XEC_INVALID_SIZE;
+ *  6. d_out or h_items NULL -> XEC_INVALID_SIZE;
+ *  7. d_out not 16-byte aligned -> XEC_INVALID_ALIGNMENT;
+ *  8. d_out's n_items*len bytes overlap the data or the parity range ->
+ *     XEC_INVALID_SIZE;
+ *  9. an item with c >= S or i >= k + m -> XEC_INVALID_COUNTS;
+ * 10. an item that is not servable -> XEC_DECODE_FAILURE;
+ * 11. more than 1,024 items: d_scratch not 4-byte aligned ->
+ *     XEC_INVALID_ALIGNMENT; NULL or fewer than xec_read_scratch_bytes(n_items)
+ *     bytes -> XEC_INVALID_SIZE.
+ * A rejected call queues nothing and writes nothing.  Up to 1,024 items travel
+ * in the kernel arguments (capacities 64 / 256 / 1024) with one bit per item
+ * saying "reconstruct" (the item word has no spare bit at S = 2^24): nothing
+ * is copied and d_scratch may be NULL.  A longer list is staged in the pinned
+ * memory the library keeps -- the items, then their bits -- and uploaded on
+ * `stream` itself into d_scratch in one copy.  h_bitmap and h_items are read
+ * before the call returns; the call is asynchronous on `stream`.  Not
+ * capturable, as xec_repair: on a capturing stream a call with work returns
+ * XEC_DEVICE_ERROR with nothing queued (xec_read_device is the capturable
+ * form).  One kernel over (item, chunk of the range) tiles, chunks of 1 KiB at
+ * the default launch shape; of xec_set_launch all four arguments apply,
+ * xec_set_rotation does not. */
+xec_status xec_read(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                    size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n_items,
+                    size_t offset, size_t len, void* d_out, void* d_scratch, size_t scratch_bytes,
+                    hipStream_t stream);
+
+/* Scratch bytes xec_read needs for a list of n_items: 4 * (n_items +
+ * ceil(n_items / 32)), the items and one bit each.  Needed only past 1,024
+ * items. */
+size_t xec_read_scratch_bytes(size_t n_items);
+
+/* Device-resident form of xec_read: bitmap and items in device memory, no host
+ * work, so it can be captured in a hipGraph; a replay serves whatever d_items
+ * and d_bitmap hold at replay time.  d_bitmap == NULL: everything present, a
+ * pure gather.  Enqueues on `stream`: *d_status = 0 (a memset, as
+ * xec_decode_device); a check kernel over the items that leaves *d_status at
+ * the MAXIMUM over the items of 0 (servable), 3 (c >= S or i >= k + m; such an
+ * item is never dereferenced) and 4 (in range but not servable); then the read
+ * kernel, which does nothing if *d_status != 0 (all-or-nothing over the
+ * requested items) and otherwise delivers the bytes xec_read delivers for the
+ * same items.
+ * Host checks, before anything is queued, in this order: XEC_NOT_INITIALIZED;
+ * xec_check_args; d_status NULL or not 4-byte aligned -> XEC_INVALID_ALIGNMENT;
+ * n_items == 0 or S == 0 -> XEC_SUCCESS with only *d_status = 0 queued;
+ * steps 4 to 8 of xec_read with d_items in h_items' place; d_items not 4-byte
+ * aligned -> XEC_INVALID_ALIGNMENT.  No limit on n_items and no scratch. */
+xec_status xec_read_device(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                           size_t m, const uint8_t* d_bitmap, const uint32_t* d_items,
+                           size_t n_items, size_t offset, size_t len, void* d_out,
+                           int32_t* d_status, hipStream_t stream);
+
+/* Host-only scan xec_read runs over its items (no GPU and no xec_init needed):
+ * XEC_INVALID_COUNTS if an item has c >= S or i >= k + m (or k, m are invalid
+ * as in xec_check_args, or h_items is NULL with n_items > 0), else
+ * XEC_DECODE_FAILURE if an item is not servable, else XEC_SUCCESS with
+ * *n_lost (may be NULL) = the number of items that need a reconstruction, a
+ * repeated item counted each time.  h_bitmap == NULL: everything is present.
+ * Only the blocks of the requested items' classes are looked at. */
+xec_status xec_check_read_items(const uint8_t* h_bitmap, size_t S, size_t k, size_t m,
+                                const uint32_t* h_items, size_t n_items, size_t* n_lost);
+
+/* Diagnostics: which tiling the calling thread's most recent xec_read or
+ * xec_read_device launched -- 0 none (an error, or nothing to read),
+ * XEC_TILING_ARG_LIST or XEC_TILING_LIST (xec_read), XEC_TILING_LIST
+ * (xec_read_device; enum below).  The other *_tiling_used values are not
+ * affected. */
+int xec_read_tiling_used(void);
+
 /* Host-only recoverability scan used by xec_decode (no GPU needed):
  * returns XEC_DECODE_FAILURE if some stripe is unrecoverable, else
  * XEC_SUCCESS and sets *needs_recovery to 1 iff some stripe needs recovery. */
@@ -466,7 +561,9 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * for other member counts none below 8, 4 below 20, 2 below 56, else 1;
  * none at 1 and 2.  The repair kernels take the same table;
  * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels and
- * the digest kernel run uncapped at every k/m (their own sweeps).  The reserved LDS keeps other kernels' LDS
+ * the digest kernel run uncapped at every k/m (their own sweeps); the read
+ * kernel takes the table, except that an xec_read whose items are all present
+ * runs uncapped.  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
  * 0..8. */
 xec_status xec_set_occupancy(int waves_per_simd);
@@ -507,7 +604,9 @@ xec_status xec_set_validate_kernel(int mode);
  * (q + c*tiles) mod (chunks per block): a permutation of each block's chunks,
  * so results are identical; it changes which columns of the stripes in flight
  * together are read at once.  0 = automatic (the measured default), -1 = none,
- * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20. */
+ * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
+ * It does not apply to xec_read / xec_read_device: their tiles walk the chunks
+ * of each item's byte range, not a column of every stripe. */
 xec_status xec_set_rotation(int tiles);
 
 /* The calling thread's overrides above as one value.  A caller that fans its
@@ -548,8 +647,8 @@ int xec_decode_arg_capacity_used(void);
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
- * xec_digest or xec_locate call
- * launches its encode / decode / repair / verify / update / digest kernel with hipExtLaunchKernel and these two
+ * xec_digest, xec_locate, xec_read or xec_read_device call
+ * launches its encode / decode / repair / verify / update / digest / read kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
  * time, with no event packet queued between kernels (a hipEventRecord between
