@@ -1561,6 +1561,137 @@ xec_status xec_read_device(const void* d_data, const void* d_parity, size_t S, s
   return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
 }
 
+// ---- ranged update with digest upkeep ------------------------------------------------
+// xec_update_range / xec_update_range_device: xec_update over bytes
+// [offset, offset + len) of each named block, and with d_digests the stored
+// digests of the touched data and parity blocks follow in the same pass
+// (xec_kernels.hip, ranged update).  Residency is uncapped, as the update
+// kernels: a lane has the same 3-5 loads in flight.  xec_digest_range_host is
+// the host's side of the upkeep identity.
+uint64_t xec_digest_range_host(const void* bytes, size_t offset, size_t len) {
+  const unsigned char* p = static_cast<const unsigned char*>(bytes);
+  const uint64_t n0 = offset / 8;
+  uint64_t sum = 0;
+  for (size_t n = 0; n < len / 8; ++n) {
+    uint64_t w = 0;
+    for (int b = 7; b >= 0; --b) w = (w << 8) | p[8 * n + (size_t)b];  // little-endian
+    sum += xec::splitmix_at(w, n0 + n);
+  }
+  return sum;
+}
+
+// Steps 5 to 8 of include/xec.h's list, shared by both forms; `new_bytes` is
+// the extent of d_new (n_items*len packed, or the shadow's S*k*bs).
+static xec_status update_range_check(const void* d_data, const void* d_parity, const void* d_new,
+                                     size_t new_bytes, const void* sel, size_t S, size_t bs,
+                                     size_t k, size_t m, size_t offset, size_t len,
+                                     const uint64_t* d_digests) {
+  if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset > bs || len > bs - offset)
+    return XEC_INVALID_SIZE;
+  if (d_new == nullptr || sel == nullptr) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_new) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(d_digests) % 8 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (ranges_overlap(d_new, new_bytes, d_data, S * k * bs) ||
+      ranges_overlap(d_new, new_bytes, d_parity, S * m * bs))
+    return XEC_INVALID_SIZE;
+  if (d_digests != nullptr) {
+    const size_t dig_bytes = 8 * S * (k + m);
+    if (ranges_overlap(d_digests, dig_bytes, d_data, S * k * bs) ||
+        ranges_overlap(d_digests, dig_bytes, d_parity, S * m * bs) ||
+        ranges_overlap(d_digests, dig_bytes, d_new, new_bytes))
+      return XEC_INVALID_SIZE;
+  }
+  return XEC_SUCCESS;
+}
+
+static xec_status update_range_impl(void* d_data, void* d_parity, const void* d_new, size_t S,
+                                    size_t bs, size_t k, size_t m, const uint32_t* h_items,
+                                    size_t n, size_t offset, size_t len, uint64_t* d_digests,
+                                    void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
+  g_update_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (n == 0 || S == 0) return XEC_SUCCESS;
+  if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  if (len != 0 && n > SIZE_MAX / len) return XEC_INVALID_SIZE;
+  st = update_range_check(d_data, d_parity, d_new, n * len, h_items, S, bs, k, m, offset, len,
+                          d_digests);
+  if (st != XEC_SUCCESS) return st;
+  for (size_t t = 0; t < n; ++t) {  // strictly ascending = batch order, no duplicates
+    const uint32_t it = h_items[t];
+    if ((it & 0xFFu) >= k || (it >> 8) >= S || (t > 0 && it <= h_items[t - 1]))
+      return XEC_INVALID_COUNTS;
+  }
+  const bool in_args = n <= xec::kArgItems;
+  if (!in_args) {
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+    if (d_scratch == nullptr || scratch_bytes < xec_update_scratch_bytes(n))
+      return XEC_INVALID_SIZE;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_update_tiling_used = XEC_TILING_ARG_LIST;
+    const hipError_t le =
+        xec::launch_update_range(d_data, d_parity, d_new, nullptr, d_digests, g, ls,
+                                 xec::kUpdateArgListTiles, offset, len, stream, n, h_items);
+    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  }
+  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
+  if (!sd.ok()) return DEVERR(hipSuccess);
+  bool fault = false;
+  Staging* sg = stage_acquire(n * 4, sd.device(), &fault);
+  if (sg == nullptr) return DEVERR(hipSuccess);
+  std::memcpy(sg->host, h_items, n * 4);
+  g_update_tiling_used = XEC_TILING_LIST;
+  hipError_t le = hipMemcpyAsync(d_scratch, sg->host, n * 4, hipMemcpyHostToDevice, stream);
+  const bool queued = le == hipSuccess;
+  if (queued)
+    le = xec::launch_update_range(d_data, d_parity, d_new, d_scratch, d_digests, g, ls,
+                                  xec::kUpdateListTiles, offset, len, stream, n);
+  stage_release(sg, queued, stream, false);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
+xec_status xec_update_range(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                            size_t k, size_t m, const uint32_t* h_items, size_t n_items,
+                            size_t offset, size_t len, uint64_t* d_digests, void* d_scratch,
+                            size_t scratch_bytes, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  try {  // as xec_decode
+    return update_range_impl(d_data, d_parity, d_new, S, bs, k, m, h_items, n_items, offset, len,
+                             d_digests, d_scratch, scratch_bytes, stream);
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_new, size_t S,
+                                   size_t bs, size_t k, size_t m, const uint8_t* d_mask,
+                                   size_t offset, size_t len, uint64_t* d_digests,
+                                   hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_update_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  // every argument is checked before any work is queued on the stream
+  st = update_range_check(d_data, d_parity, d_new, S * k * bs, d_mask, S, bs, k, m, offset, len,
+                          d_digests);
+  if (st != XEC_SUCCESS) return st;
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  g_update_tiling_used = XEC_TILING_CLASS;
+  const hipError_t le =
+      xec::launch_update_range(d_data, d_parity, d_new, d_mask, d_digests, g, ls,
+                               xec::kUpdateClassTiles, offset, len, stream);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
   if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;

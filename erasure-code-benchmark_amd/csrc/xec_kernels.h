@@ -109,7 +109,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
 }
 
 // The codec kernels (encode, every decode, repair and update tiling, verify,
-// digest, read) go through this: as launch(), but with the thread's pending kernel events,
+// digest, read, ranged update) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -256,6 +256,21 @@ hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out, co
 // of its class lost too).  The caller zeroes *d_status first, stream-ordered.
 hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
                              const Geometry& g, int32_t* d_status, hipStream_t s);
+// Ranged update (xec_update_range, xec_update_range_device): launch_update over
+// bytes [offset, offset + len) of each named block only, tilings and d_sel /
+// h_items as there (kUpdate*Tiles); a tile is (list position or class, chunk of
+// the RANGE), chunks of 16*threads*unroll bytes.  List forms: item t's new
+// bytes are the len bytes at d_new + t*len; class form: d_new mirrors d_data.
+// d_digests != nullptr (S*(k+m) u64, xec_digest's layout) adds
+// mix(new) - mix(old) over the range's words to the slot of every updated data
+// block and of the parity block of every class with an item, one 64-bit
+// atomicAdd per wave and slot; nullptr launches instantiations without any of
+// it.  offset, len % 16 == 0, len > 0, offset + len <= bs.  Of g only S, k, m,
+// nm and bs are used; no column rotation.
+hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
+                               uint64_t* d_digests, const Geometry& g, const LaunchShape& ls,
+                               int tiling, uint64_t offset, uint64_t len, hipStream_t s,
+                               uint64_t n_items = 0, const uint32_t* h_items = nullptr);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

@@ -1760,6 +1760,297 @@ hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, u
                 d_items, n, g, d_status);
 }
 
+// ---------------------------------------------------------------------------
+// ranged update (xec_update_range, xec_update_range_device).  Kernels and
+// launchers together, after every older one, so the older kernels keep their
+// place.
+//
+// The update above over bytes [offset, offset + len) of each named block only,
+//   parity[c][i % m][range] ^= data[c][i][range] ^ new;   data[c][i][range] = new
+// with the read's range addressing: a tile is (list position or class, chunk
+// of the RANGE), chunk q covers block offsets offset + q*16*T*U onwards and
+// g.tiles_per_block counts the chunks of the range.  A lane's granule is never
+// formed below `offset` and takes part only while below offset + len.
+// Ownership is update's: the first item of a class in its stripe owns that
+// class's parity chunk and folds the later ones, one lane owns a granule, and
+// both stores go in place through st16_block (data sc1, parity nt).  These are
+// update_list_tile / fold_member written again, not shared with them: the old
+// kernels stay instruction for instruction what they were.
+//
+// New bytes.  List forms: item e's len bytes are packed at fresh + e*len, so a
+// granule at block offset o is read from fresh + e*len + (o - offset).  Class
+// form: fresh mirrors data, the granule comes from the same in-block address.
+//
+// DIG = true keeps the stored digests current in the same pass (xec_digest's
+// slots, c*(k+m) + i).  digest(block) is a sum of per-word terms, so a write
+// of some words changes it by sum(mix(new)) - sum(mix(old)) over those words,
+// and the tile holds both sides in registers:
+//   data slot    += mix(new granule) - mix(old granule), per folded member;
+//   parity slot  += mix(parity after) - mix(parity before); the `before` term
+//                   is subtracted when the parity is loaded, so no second copy
+//                   of it stays in registers.
+// Each lane sums over its granules (word index n = in-block byte address / 8),
+// a wave reduces with shuffles and ONE lane per wave does ONE 64-bit atomicAdd
+// into the slot (none when the wave's sum is 0, e.g. a write of equal bytes):
+// ceil(len / (16*T*U)) * T/64 adds per slot, i.e. one per KiB of the range at
+// the default shape.  The sum is modulo 2^64, so the order of tiles does not
+// matter.  DIG = false is a separate instantiation with no multiply and no
+// atomic in it.
+// ---------------------------------------------------------------------------
+constexpr int kPatchDataStoreAux = 16;   // sc1, as update
+constexpr int kPatchParityStoreAux = 2;  // nt, as update
+
+// One wave's sum of x goes to *slot.  Called from wave-uniform control flow.
+__device__ __forceinline__ void patch_wave_add(uint64_t* slot, uint64_t x) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
+  if ((threadIdx.x & 63u) == 0 && x != 0)
+    atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)x);
+}
+
+// Digest terms of this lane's active granules; z = (n + 1) * golden of the
+// first word of granule 0, granule u is 2*T words on.
+template <int U, int T>
+__device__ __forceinline__ uint64_t patch_mix(const u32x4 (&v)[U], uint64_t off, uint64_t end,
+                                              uint64_t z) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  constexpr uint64_t kStepZ = (uint64_t)(2 * T) * kSplitmixGolden;
+  uint64_t s = 0;
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) s += digest_granule(v[u], z + u * kStepZ);
+  return s;
+}
+
+// acc ^= old ^ new over this lane's granules of the range of one data block,
+// which takes the new bytes; `fr` = the new bytes of this lane's granule 0.
+// Returns mix(new) - mix(old) over them (DIG), else 0.
+template <int U, bool NT, int T, bool DIG>
+__device__ __forceinline__ uint64_t patch_fold(u32x4 (&acc)[U], uint8_t* block, const uint8_t* fr,
+                                               uint64_t off, uint64_t end, uint64_t z) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  u32x4 o[U], n[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) o[u] = ld16<NT>(block + off + u * kStep);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) n[u] = ld16<NT>(fr + u * kStep);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) acc[u] ^= o[u] ^ n[u];
+  uint64_t d = 0;
+  if constexpr (DIG) d = patch_mix<U, T>(n, off, end, z) - patch_mix<U, T>(o, off, end, z);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) st16_block<NT, kPatchDataStoreAux>(block, off + u * kStep, n[u]);
+  return d;
+}
+
+// List tiles: one per (list position e, chunk of the range), ownership as
+// update_list_tile.
+template <int U, bool NT, int T, bool DIG, typename At>
+__device__ __forceinline__ void patch_list_tile(uint8_t* data, uint8_t* parity,
+                                                const uint8_t* __restrict__ fresh,
+                                                uint64_t* digests, uint64_t e, uint64_t n,
+                                                uint64_t chunk, const ReadRange& rr,
+                                                const Geometry& g, At at) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t m = (uint32_t)g.m;
+  const uint32_t item = at(e);
+  const uint32_t c = item >> 8, j = (item & 0xFFu) % m;
+  for (uint64_t q = e; q > 0;) {
+    const uint32_t prev = at(--q);
+    if ((prev >> 8) != c) break;
+    if ((prev & 0xFFu) % m == j) return;  // an earlier item's tile folds this one
+  }
+  const uint64_t end = rr.offset + rr.len;
+  const uint64_t rel = (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;  // from the range's start
+  const uint64_t off = rr.offset + rel;
+  const uint64_t z = (off / 8 + 1) * kSplitmixGolden;
+  uint8_t* par = parity + ((uint64_t)c * g.m + j) * g.bs;
+  uint64_t* row = digests + (uint64_t)c * (g.k + g.m);
+  u32x4 acc[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) acc[u] = ld16<NT>(par + off + u * kStep);
+  uint64_t psum = 0;
+  if constexpr (DIG) psum = 0 - patch_mix<U, T>(acc, off, end, z);
+  uint32_t it = item;
+  for (uint64_t q = e;;) {
+    const uint32_t i = it & 0xFFu;
+    if (i % m == j) {
+      const uint64_t d = patch_fold<U, NT, T, DIG>(acc, data + ((uint64_t)c * g.k + i) * g.bs,
+                                                   fresh + q * rr.len + rel, off, end, z);
+      if constexpr (DIG) patch_wave_add(row + i, d);
+    }
+    if (++q == n) break;
+    it = at(q);
+    if ((it >> 8) != c) break;
+  }
+  if constexpr (DIG) psum += patch_mix<U, T>(acc, off, end, z);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (off + u * kStep < end) st16_block<NT, kPatchParityStoreAux>(par, off + u * kStep, acc[u]);
+  if constexpr (DIG) patch_wave_add(row + g.k + j, psum);
+}
+
+template <int U, bool NT, int T, bool DIG>
+__global__ __launch_bounds__(T) void patch_list_kernel(uint8_t* data, uint8_t* parity,
+                                                       const uint8_t* __restrict__ fresh,
+                                                       const uint32_t* __restrict__ items,
+                                                       uint64_t* digests, ReadRange rr,
+                                                       Geometry g) {
+  const uint64_t n = g.total_tiles / g.tiles_per_block;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as update_list_kernel
+    patch_list_tile<U, NT, T, DIG>(data, parity, fresh, digests, t / g.tiles_per_block, n,
+                                   t % g.tiles_per_block, rr, g,
+                                   [&](uint64_t q) { return *(const_u32_as4)(items + q); });
+  }
+}
+
+template <int U, bool NT, int T, bool DIG, uint32_t CAP>
+__global__ __launch_bounds__(T) void patch_arglist_kernel(uint8_t* data, uint8_t* parity,
+                                                          const uint8_t* __restrict__ fresh,
+                                                          uint64_t* digests, ReadRange rr,
+                                                          Geometry g, ArgItems<CAP> items) {
+  const uint64_t n = g.total_tiles / g.tiles_per_block;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    patch_list_tile<U, NT, T, DIG>(data, parity, fresh, digests, t / g.tiles_per_block, n,
+                                   t % g.tiles_per_block, rr, g,
+                                   [&](uint64_t q) { return items.v[q]; });
+  }
+}
+
+// Class tiles over a device mask (xec_update_range_device), as
+// update_class_kernel: (stripe, class, chunk of the range); fresh mirrors data.
+template <int U, bool NT, int T, bool DIG>
+__global__ __launch_bounds__(T) void patch_class_kernel(uint8_t* data, uint8_t* parity,
+                                                        const uint8_t* __restrict__ fresh,
+                                                        const uint8_t* __restrict__ mask,
+                                                        uint64_t* digests, ReadRange rr,
+                                                        Geometry g) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t nm = (uint32_t)g.nm;
+  const uint64_t stride = g.m * g.bs;
+  const uint64_t end = rr.offset + rr.len;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as update_class_kernel
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t mrow = reinterpret_cast<uint64_t>(mask + tc.c * g.k) + tc.j;
+    const uint64_t first = (tc.c * g.k + tc.j) * g.bs;
+    const uint64_t off = rr.offset + (tc.chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+    const uint64_t z = (off / 8 + 1) * kSplitmixGolden;
+    uint8_t* par = parity + (tc.c * g.m + tc.j) * g.bs;
+    uint64_t* row = digests + tc.c * (g.k + g.m);
+    u32x4 acc[U];
+    uint64_t psum = 0;
+    bool any = false;
+    for (uint32_t r = 0; r < nm; ++r) {
+      if (sbyte(mrow + (uint64_t)r * g.m) == 0) continue;
+      if (!any) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (off + u * kStep < end) acc[u] = ld16<NT>(par + off + u * kStep);
+        if constexpr (DIG) psum = 0 - patch_mix<U, T>(acc, off, end, z);
+      }
+      any = true;
+      const uint64_t d = patch_fold<U, NT, T, DIG>(acc, data + first + r * stride,
+                                                   fresh + first + r * stride + off, off, end, z);
+      if constexpr (DIG) patch_wave_add(row + tc.j + (uint64_t)r * g.m, d);
+    }
+    if (!any) continue;
+    if constexpr (DIG) psum += patch_mix<U, T>(acc, off, end, z);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (off + u * kStep < end) st16_block<NT, kPatchParityStoreAux>(par, off + u * kStep, acc[u]);
+    if constexpr (DIG) patch_wave_add(row + g.k + tc.j, psum);
+  }
+}
+
+namespace {
+
+template <int U, bool NT, int T, bool DIG>
+hipError_t launch_patch_t(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
+                          uint64_t* dig, const ReadRange& rr, const Geometry& g, int tiling,
+                          uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& al) {
+  if (tiling == kUpdateArgListTiles) {
+    switch (arg_items_capacity(al.n)) {
+      case 64:
+        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 64>, grid, T, lds, s, d, p, fresh,
+                            dig, rr, g, arg_items<64>(al.items, al.n));
+      case 256:
+        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 256>, grid, T, lds, s, d, p, fresh,
+                            dig, rr, g, arg_items<256>(al.items, al.n));
+      default:
+        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 1024>, grid, T, lds, s, d, p,
+                            fresh, dig, rr, g, arg_items<1024>(al.items, al.n));
+    }
+  }
+  if (tiling == kUpdateListTiles)
+    return launch_codec(patch_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
+                        static_cast<const uint32_t*>(sel), dig, rr, g);
+  return launch_codec(patch_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
+                      static_cast<const uint8_t*>(sel), dig, rr, g);
+}
+
+template <bool NT, int T, bool DIG>
+hipError_t patch_u(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel, uint64_t* dig,
+                   const ReadRange& rr, const Geometry& g, int tiling, int unroll, uint32_t grid,
+                   uint32_t lds, hipStream_t s, const ArgList& a) {
+  return unroll == 2
+             ? launch_patch_t<2, NT, T, DIG>(d, p, fresh, sel, dig, rr, g, tiling, grid, lds, s, a)
+             : launch_patch_t<1, NT, T, DIG>(d, p, fresh, sel, dig, rr, g, tiling, grid, lds, s, a);
+}
+
+template <bool NT, int T>
+hipError_t patch_dig(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel, uint64_t* dig,
+                     const ReadRange& rr, const Geometry& g, int tiling, int unroll, uint32_t grid,
+                     uint32_t lds, hipStream_t s, const ArgList& a) {
+  return dig != nullptr
+             ? patch_u<NT, T, true>(d, p, fresh, sel, dig, rr, g, tiling, unroll, grid, lds, s, a)
+             : patch_u<NT, T, false>(d, p, fresh, sel, dig, rr, g, tiling, unroll, grid, lds, s, a);
+}
+
+}  // namespace
+
+hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
+                               uint64_t* d_digests, const Geometry& g_class, const LaunchShape& ls,
+                               int tiling, uint64_t offset, uint64_t len, hipStream_t s,
+                               uint64_t n_items, const uint32_t* h_items) {
+  if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs ||
+      tiling < kUpdateClassTiles || tiling > kUpdateArgListTiles)
+    return hipErrorInvalidValue;
+  Geometry g = g_class;
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
+  g.total_tiles = (tiling == kUpdateClassTiles ? g.S * g.m : n_items) * g.tiles_per_block;
+  g.rot = 0;
+  if (g.total_tiles == 0) return hipSuccess;
+  if (g.k > 256 && tiling != kUpdateClassTiles) return hipErrorInvalidValue;
+  if (tiling == kUpdateArgListTiles && (n_items > kArgItems || h_items == nullptr))
+    return hipErrorInvalidValue;
+  if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
+  const ReadRange rr{offset, len};
+  const ArgList a{h_items, n_items};
+  uint8_t* d = static_cast<uint8_t*>(d_data);
+  uint8_t* p = static_cast<uint8_t*>(d_parity);
+  const uint8_t* f = static_cast<const uint8_t*>(d_new);
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt ? patch_dig<true, 256>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
+                                        lds, s, a)
+                 : patch_dig<false, 256>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
+                                         lds, s, a);
+  return ls.nt ? patch_dig<true, 64>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
+                                     lds, s, a)
+               : patch_dig<false, 64>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
+                                      lds, s, a);
+}
+
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set
 // is told once, on stderr, that every launch of the library will fail
 // (a silent hook in the shipped library).

@@ -15,7 +15,8 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     set_occupancy,
                     set_rotation, set_validate_kernel,
                     status_string, update, update_device, update_scratch_bytes,
-                    update_tiling_used, validate_blocks, verify, write_validation_pattern)
+                    update_tiling_used, validate_blocks, verify, write_validation_pattern,
+                    digest_range_host, update_range, update_range_device)
 from .partition import stripe_range
 
 __all__ = [
@@ -32,4 +33,5 @@ __all__ = [
     "set_occupancy", "set_rotation", "set_validate_kernel", "status_string", "stripe_range",
     "update", "update_device", "update_scratch_bytes", "update_tiling_used", "validate_blocks",
     "verify", "write_validation_pattern",
+    "digest_range_host", "update_range", "update_range_device",
 ]

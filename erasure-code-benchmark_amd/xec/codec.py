@@ -154,6 +154,42 @@ def digest_host(block) -> int:
     return int(lib().xec_digest_host(_ptr(block), block.nbytes))
 
 
+def digest_range_host(data, offset: int, length: int | None = None) -> int:
+    """xec_digest_range_host -- the digest terms of a range: the sum over the
+    little-endian u64 words w[n] of `data` (bytes or a C-contiguous numpy array
+    holding the range itself) of splitmix_at(w[n], offset/8 + n), mod 2^64;
+    `offset` is where the range starts in its block.  Host only."""
+    if isinstance(data, (bytes, bytearray)):
+        n = len(data) if length is None else length
+        buf = (ctypes.c_char * len(data)).from_buffer_copy(data)
+        return int(lib().xec_digest_range_host(ctypes.addressof(buf), offset, n))
+    n = data.nbytes if length is None else length
+    return int(lib().xec_digest_range_host(_ptr(data), offset, n))
+
+
+def update_range(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, h_items,
+                 n_items: int, offset: int, length: int, d_digests=None, d_scratch=None,
+                 scratch_bytes: int = 0, stream=None) -> Status:
+    """xec_update_range -- xec_update over bytes [offset, offset + length) of
+    each named block: item t's new bytes are the `length` bytes at
+    d_new + t*length.  With d_digests (S*(k+m) device uint64, xec_digest's
+    layout) the slots of the touched data and parity blocks follow in the same
+    pass; None touches no digest."""
+    return Status(lib().xec_update_range(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs, k, m,
+                                         _ptr(h_items), n_items, offset, length,
+                                         _ptr(d_digests), _ptr(d_scratch), scratch_bytes,
+                                         _stream(stream)))
+
+
+def update_range_device(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, d_mask,
+                        offset: int, length: int, d_digests=None, stream=None) -> Status:
+    """xec_update_range_device -- the same with a device mask (S*k bytes,
+    NONZERO = take the block) and d_new a shadow of d_data's layout; capturable."""
+    return Status(lib().xec_update_range_device(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs,
+                                                k, m, _ptr(d_mask), offset, length,
+                                                _ptr(d_digests), _stream(stream)))
+
+
 def digest(d_data, d_parity, S: int, bs: int, k: int, m: int, d_digests, d_select=None,
            stream=None) -> Status:
     """xec_digest -- d_digests (S*(k+m) device uint64, the bitmap's layout) =

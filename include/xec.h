@@ -492,6 +492,105 @@ xec_status xec_check_read_items(const uint8_t* h_bitmap, size_t S, size_t k, siz
  * affected. */
 int xec_read_tiling_used(void);
 
+/* Ranged update with digest upkeep (no reference counterpart): xec_update
+ * over bytes [offset, offset + len) of each named block only, following
+ * xec_read's range rules.  For every named block i of stripe c,
+ *     parity[c][i % m][range] ^= data[c][i][range] ^ new;
+ *     data[c][i][range] = new
+ * Bytes outside the range, blocks not named and parity blocks of classes
+ * without an item are neither read nor written: per item the call reads 3*len
+ * and writes 2*len bytes, where xec_update moves 5*bs.  The delta keeps a
+ * class's syndrome, as xec_update does.
+ * Items are xec_update's: h_items[t] = c << 8 | i, i < k, c < S, strictly
+ * ascending, and everything xec_update says about them holds.  Item t's new
+ * bytes are the len bytes at d_new + t*len -- xec_read's packing of d_out, on
+ * the input side.  Up to 1,024 items travel in the kernel arguments
+ * (capacities 64 / 256 / 1024); a longer list goes through the pinned staging
+ * into d_scratch (xec_update_scratch_bytes(n_items) bytes) in one copy on
+ * `stream`.  Not capturable, as xec_update: on a capturing stream a call with
+ * work returns XEC_DEVICE_ERROR with nothing queued.
+ *
+ * Digest upkeep.  d_digests == NULL: no digest is touched, and the kernel that
+ * runs has no digest code in it.  Otherwise d_digests is S*(k+m) u64 in
+ * xec_digest's layout, 8-byte aligned, and in the same pass
+ *  - the slot of each updated data block gets
+ *        += sum_n splitmix_at(new w[n], n) - sum_n splitmix_at(old w[n], n)
+ *    over the words n of the range (n counted from the start of the block);
+ *  - the parity slot c*(k+m) + k + j of each class with an item gets the same
+ *    difference over the parity bytes after and before;
+ * so slots that held the digests of the blocks before the call hold the
+ * digests of the blocks after it, bit-exact against xec_digest_host.  Slots of
+ * other blocks are neither read nor written.  The adds are 64-bit atomics
+ * (one per wave and slot, i.e. one per KiB of the range and slot at the
+ * default launch shape), so the order of tiles does not matter.  With
+ * offset = 0, len = bs this is the one-pass form of xec_update followed by
+ * xec_digest(select).  A whole 1 MiB block then sends 1,024 adds to one slot,
+ * which costs time (config 3: about 1.5x the same call without upkeep), but
+ * the one pass still measured faster than the two at configs 2, 3 and 4
+ * (DESIGN.md §3 *Ranged update*).
+ *
+ * What upkeep keeps, and what it cannot know.
+ *  - A slot that disagreed with its block before the call disagrees by the
+ *    same amount after it.  Upkeep never blesses damage, and a stale digest
+ *    stays stale.
+ *  - If the old bytes inside the range were already damaged, the delta is
+ *    taken from the damaged bytes.  The data block now holds exactly the new
+ *    bytes, the damage has moved into the parity block (its class stays
+ *    flagged by xec_verify), and the data block's slot keeps disagreeing.
+ *  - xec_locate then names the data block, and xec_repair_device would rebuild
+ *    it from a parity that carries the damage.  A second xec_locate after the
+ *    repair still counts the block: rebuilt blocks do not match their stored
+ *    digest in this one case.
+ *  - This is inherent in an incremental checksum.  A caller that cannot accept
+ *    it passes d_digests = NULL and refreshes with xec_digest(select), at the
+ *    price of reading the whole blocks.
+ *
+ * Checks, all on the host before anything is queued, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. xec_check_args;
+ *  3. n_items == 0 or S == 0 -> XEC_SUCCESS, nothing queued;
+ *  4. k > 256 or S > 2^24 -> XEC_INVALID_SIZE (the packing);
+ *  5. len == 0, offset % 16, len % 16 or offset + len > bs -> XEC_INVALID_SIZE;
+ *  6. d_new or h_items NULL -> XEC_INVALID_SIZE;
+ *  7. d_new not 16-byte aligned, or d_digests not NULL and not 8-byte aligned
+ *     -> XEC_INVALID_ALIGNMENT;
+ *  8. d_new's n_items*len bytes overlap the data or the parity range, or
+ *     d_digests' 8*S*(k+m) bytes overlap data, parity or d_new ->
+ *     XEC_INVALID_SIZE (ranges that only touch are allowed);
+ *  9. the item rules of xec_update -> XEC_INVALID_COUNTS;
+ * 10. more than 1,024 items: the scratch rules of xec_update.
+ * A rejected call queues nothing and changes nothing.  One kernel over (list
+ * position, chunk of the range) tiles; xec_update_tiling_used reports as for
+ * xec_update; of xec_set_launch all four arguments apply, xec_set_rotation
+ * does not; residency is uncapped. */
+xec_status xec_update_range(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                            size_t k, size_t m, const uint32_t* h_items, size_t n_items,
+                            size_t offset, size_t len, uint64_t* d_digests, void* d_scratch,
+                            size_t scratch_bytes, hipStream_t stream);
+
+/* Device-resident form of xec_update_range: no host work, so it can be
+ * captured in a hipGraph, and no limit on k or S.  d_mask is S*k device bytes,
+ * NONZERO = take the block (xec_update_device's mask); d_new is a shadow
+ * mirroring d_data's layout (S*k*bs bytes), of which only [offset,
+ * offset + len) of the marked blocks is read.  One kernel over (stripe, class,
+ * chunk of the range) tiles; xec_update_tiling_used reports XEC_TILING_CLASS.
+ * Checks: 1, 2, S == 0 -> XEC_SUCCESS with nothing queued, then 5, d_new or
+ * d_mask NULL -> XEC_INVALID_SIZE, 7 and 8 with d_new's extent S*k*bs. */
+xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_new, size_t S,
+                                   size_t bs, size_t k, size_t m, const uint8_t* d_mask,
+                                   size_t offset, size_t len, uint64_t* d_digests,
+                                   hipStream_t stream);
+
+/* The digest terms of a range: the sum over the len/8 little-endian words w[n]
+ * at `bytes` of splitmix_at(w[n], offset/8 + n)  (mod 2^64) -- `bytes` points
+ * at the range's first byte, `offset` is where that byte sits in its block.
+ * Host only, no xec_init needed; offset % 8 == 0 and len % 8 == 0 (tails are
+ * ignored as in xec_digest_host).  xec_digest_host(b, bs) ==
+ * xec_digest_range_host(b, 0, bs); the function is additive over any split of
+ * a range; and the upkeep above is range(new) - range(old), so a caller that
+ * patches host-side copies can keep its digests the same way. */
+uint64_t xec_digest_range_host(const void* bytes, size_t offset, size_t len);
+
 /* Host-only recoverability scan used by xec_decode (no GPU needed):
  * returns XEC_DECODE_FAILURE if some stripe is unrecoverable, else
  * XEC_SUCCESS and sets *needs_recovery to 1 iff some stripe needs recovery. */
@@ -605,8 +704,9 @@ xec_status xec_set_validate_kernel(int mode);
  * so results are identical; it changes which columns of the stripes in flight
  * together are read at once.  0 = automatic (the measured default), -1 = none,
  * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
- * It does not apply to xec_read / xec_read_device: their tiles walk the chunks
- * of each item's byte range, not a column of every stripe. */
+ * It does not apply to xec_read / xec_read_device and xec_update_range /
+ * xec_update_range_device: their tiles walk the chunks of each item's byte
+ * range, not a column of every stripe. */
 xec_status xec_set_rotation(int tiles);
 
 /* The calling thread's overrides above as one value.  A caller that fans its
@@ -647,7 +747,8 @@ int xec_decode_arg_capacity_used(void);
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
- * xec_digest, xec_locate, xec_read or xec_read_device call
+ * xec_digest, xec_locate, xec_read, xec_read_device, xec_update_range or
+ * xec_update_range_device call
  * launches its encode / decode / repair / verify / update / digest / read kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
