@@ -1692,6 +1692,115 @@ xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_n
   return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
 }
 
+// ---- degraded write --------------------------------------------------------------------
+// xec_write / xec_write_device: xec_update_range under a loss bitmap
+// (xec_kernels.hip, degraded write).  The host scan hands every item two bits
+// (its block lost, its class's parity lost); they travel with the list as
+// xec_read's loss bits do.  Residency is uncapped in every mode: the sweep of
+// the rebuild mode is recorded in DESIGN.md §3 *Degraded write*.
+static thread_local int g_write_tiling_used = 0;  // xec_write_tiling_used: this thread's last write
+
+static xec_status write_impl(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                             size_t k, size_t m, const uint8_t* h_bitmap, const uint32_t* h_items,
+                             size_t n, size_t offset, size_t len, uint64_t* d_digests,
+                             void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
+  g_write_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (n == 0 || S == 0) return XEC_SUCCESS;
+  if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  if (len != 0 && n > SIZE_MAX / len) return XEC_INVALID_SIZE;
+  st = update_range_check(d_data, d_parity, d_new, n * len, h_items, S, bs, k, m, offset, len,
+                          d_digests);
+  if (st != XEC_SUCCESS) return st;
+  const bool in_args = n <= xec::kArgItems;
+  uint32_t short_bits[xec::kArgItems / 16];
+  st = xec_scan_write_items(h_bitmap, S, k, m, h_items, n, in_args ? short_bits : nullptr, nullptr,
+                            nullptr);
+  if (st != XEC_SUCCESS) return st;
+  if (!in_args) {
+    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+    if (d_scratch == nullptr || scratch_bytes < xec_write_scratch_bytes(n))
+      return XEC_INVALID_SIZE;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_write_tiling_used = XEC_TILING_ARG_LIST;
+    const hipError_t le =
+        xec::launch_write(d_data, d_parity, d_new, nullptr, nullptr, d_digests, g, ls,
+                          xec::kUpdateArgListTiles, offset, len, stream, n, h_items, short_bits);
+    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  }
+  // items, then their loss bits, staged in pinned memory and uploaded on
+  // `stream` itself in one copy, as xec_read uploads its list
+  const StreamDevice sd(stream);
+  if (!sd.ok()) return DEVERR(hipSuccess);
+  bool fault = false;
+  const size_t bytes = xec_write_scratch_bytes(n);
+  Staging* sg = stage_acquire(bytes, sd.device(), &fault);
+  if (sg == nullptr) return DEVERR(hipSuccess);
+  uint32_t* staged = static_cast<uint32_t*>(sg->host);
+  std::memcpy(staged, h_items, n * 4);
+  (void)xec_scan_write_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr, nullptr);
+  g_write_tiling_used = XEC_TILING_LIST;
+  hipError_t le = hipMemcpyAsync(d_scratch, staged, bytes, hipMemcpyHostToDevice, stream);
+  const bool queued = le == hipSuccess;
+  if (queued)
+    le = xec::launch_write(d_data, d_parity, d_new, d_scratch, nullptr, d_digests, g, ls,
+                           xec::kUpdateListTiles, offset, len, stream, n);
+  stage_release(sg, queued, stream, false);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
+xec_status xec_write(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs, size_t k,
+                     size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n_items,
+                     size_t offset, size_t len, uint64_t* d_digests, void* d_scratch,
+                     size_t scratch_bytes, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  try {  // as xec_decode
+    return write_impl(d_data, d_parity, d_new, S, bs, k, m, h_bitmap, h_items, n_items, offset,
+                      len, d_digests, d_scratch, scratch_bytes, stream);
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+size_t xec_write_scratch_bytes(size_t n_items) { return 4 * xec::write_list_words(n_items); }
+
+int xec_write_tiling_used(void) { return g_write_tiling_used; }
+
+xec_status xec_write_device(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                            size_t k, size_t m, const uint8_t* d_bitmap, const uint8_t* d_mask,
+                            size_t offset, size_t len, uint64_t* d_digests, int32_t* d_status,
+                            hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_write_tiling_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  // every argument is checked before any work is queued on the stream
+  st = update_range_check(d_data, d_parity, d_new, S * k * bs, d_mask, S, bs, k, m, offset, len,
+                          d_digests);
+  if (st != XEC_SUCCESS) return st;
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_write_check(d_bitmap, d_mask, g, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  g_write_tiling_used = XEC_TILING_CLASS;
+  const hipError_t le =
+      xec::launch_write(d_data, d_parity, d_new, d_mask, d_bitmap, d_digests, g, ls,
+                        xec::kUpdateClassTiles, offset, len, stream);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
   if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;

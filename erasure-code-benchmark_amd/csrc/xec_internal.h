@@ -73,6 +73,21 @@ xec_status xec_scan_read_items(const uint8_t* bm, size_t S, size_t k, size_t m,
                                const uint32_t* items, size_t n_items, uint32_t* lost_bits,
                                size_t* n_lost);
 
+// Write scan (xec_write; xec_check_write_items is this with bits null): the
+// verdict over the n_items WRITTEN items c << 8 | i, i < k, strictly ascending.
+// XEC_INVALID_COUNTS if any item breaks xec_update's item rules (i >= k,
+// c >= S, not ascending; or k, m as xec_check_args, or items null with
+// n_items > 0) anywhere in the list, else XEC_DECODE_FAILURE if any item is not
+// servable (xec_scan_read_items' rule).  On success *n_rebuild (may be null) =
+// the lost items, *n_data_only (may be null) = the items whose class lost its
+// parity block, and, when bits is non-null, its (n_items + 15) / 16 words hold
+// two bits per item, item t at bits 2*(t % 16) of word t / 16: bit 0 = the
+// block is lost, bit 1 = its class's parity block is lost.  Defined in
+// xec_scan.cpp.
+xec_status xec_scan_write_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                                const uint32_t* items, size_t n_items, uint32_t* bits,
+                                size_t* n_rebuild, size_t* n_data_only);
+
 // masks[c] = bit i set iff data byte i of stripe c's row is 0 (lost), for the
 // kernel-argument mask decode (xec_kernels.hip decode_argmask_kernel).
 // Requires k <= 32; the rows must already have passed xec_scan_bitmap (no

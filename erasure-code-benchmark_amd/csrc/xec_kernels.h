@@ -109,7 +109,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
 }
 
 // The codec kernels (encode, every decode, repair and update tiling, verify,
-// digest, read, ranged update) go through this: as launch(), but with the thread's pending kernel events,
+// digest, read, ranged update, degraded write) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -271,6 +271,35 @@ hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, 
                                uint64_t* d_digests, const Geometry& g, const LaunchShape& ls,
                                int tiling, uint64_t offset, uint64_t len, hipStream_t s,
                                uint64_t n_items = 0, const uint32_t* h_items = nullptr);
+// Degraded write (xec_write, xec_write_device): launch_update_range under a
+// loss bitmap -- a lost block is never read and never written.  Tilings, d_sel,
+// h_items, d_new's packing, the range and d_digests as there (kUpdate*Tiles).
+// The tile that owns a (stripe, class) runs it in one of three modes: delta
+// (parity present, no written member lost: the ranged update), data-only
+// (parity lost: written members take their bytes, parity untouched) or
+// rebuild (one written member lost, the rest of the class present: parity's
+// range recomputed from new and unwritten members, the lost block untouched).
+// Where the mode comes from:
+//   kUpdateArgListTiles  h_bits by value beside h_items: two bits per item, 16
+//                        items per word, bit 0 = this block is lost, bit 1 =
+//                        its class's parity block is lost (n <= kArgItems);
+//   kUpdateListTiles     d_sel = n u32 items followed by (n + 15) / 16 words of
+//                        the same bits (write_list_words(n) words in all);
+//   kUpdateClassTiles    d_sel = the S*k mask bytes, d_bitmap = the batch bitmap
+//                        (byte 0 = lost) or nullptr (everything present); g.gate
+//                        must be set (launch_write_check's verdict).
+// Every item must be servable (the caller or the check kernel saw to it).
+inline uint64_t write_list_words(uint64_t n) { return n + (n + 15) / 16; }
+hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
+                        const uint8_t* d_bitmap, uint64_t* d_digests, const Geometry& g,
+                        const LaunchShape& ls, int tiling, uint64_t offset, uint64_t len,
+                        hipStream_t s, uint64_t n_items = 0, const uint32_t* h_items = nullptr,
+                        const uint32_t* h_bits = nullptr);
+// xec_write_device's verdict: *d_status = 4 if a marked block is lost while
+// another block of its class is lost.  The caller zeroes *d_status first,
+// stream-ordered; d_bitmap == nullptr launches nothing.
+hipError_t launch_write_check(const uint8_t* d_bitmap, const uint8_t* d_mask, const Geometry& g,
+                              int32_t* d_status, hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

@@ -2051,6 +2051,508 @@ hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, 
                                       lds, s, a);
 }
 
+// ---------------------------------------------------------------------------
+// degraded write (xec_write, xec_write_device).  Kernels and launchers
+// together, after every older one, so the older kernels keep their place; they
+// stand beside patch_* and share only its lane helpers (patch_fold, patch_mix,
+// patch_wave_add), so the patch kernels stay what they were.
+//
+// The ranged update above under a loss bitmap: a lost block is never read and
+// never written.  Tiles, range addressing, ownership (the first item of a
+// (stripe, class) owns the class's parity granules and folds every item of the
+// class) and store policies (new data sc1, parity nt) are the ranged update's.
+// The owning tile picks one of three modes for its class from scalar state --
+// the two loss bits that travel with each item of a host-checked list, or the
+// class's mask and bitmap bytes in the device form -- so the branch is uniform
+// per workgroup:
+//   delta      parity present, no written member lost: patch_list_tile's body.
+//              A lost member that is not written is not touched.
+//   data-only  parity lost: each written (present) member takes its new bytes,
+//              parity is neither read nor written.  The old bytes are read only
+//              with DIG.
+//   rebuild    one written member x lost, every other block present:
+//                parity[range] = XOR over all members r of
+//                                (new_r if r is written else data_r)[range]
+//              -- x's term is new_x, so every member has a source and x itself
+//              is never addressed.  Present written members take their new
+//              bytes from the registers the reduction loaded.  The member count
+//              is a run-time loop, 8 loads in flight per granule (the ragged
+//              path of xor_members_to): no member-count template parameter.
+//              Old parity is read only with DIG.
+// Which members are written: the list is ascending, so walking members 0..nm-1
+// beside the list is a merge (ListWritten); the class form reads the mask byte.
+//
+// DIG in the rebuild mode.  Present written member: += mix(new) - mix(old), as
+// data-only.  Parity: += mix(P_new) - mix(P_old).  Lost member x: its slot held
+// the digest of the bytes it virtually holds, P_old ^ XOR_{r != x} old_r, so it
+// gets += mix(new_x) - mix(P_old ^ XOR_{r != x} old_r).
+//
+// Bounds are the ranged update's: no granule below `offset` is formed, a
+// granule takes part only while below offset + len, item e's new bytes are
+// read inside [fresh + e*len, fresh + (e+1)*len).
+// ---------------------------------------------------------------------------
+constexpr int kWriteDelta = 0;
+constexpr int kWriteDataOnly = 1;
+constexpr int kWriteRebuild = 2;
+
+// Where a tile stands in its block, shared by the three modes.
+struct WriteLane {
+  uint64_t off, end, z;  // first granule's block offset, the range's end, digest z of `off`
+};
+
+// A present written block takes its new bytes; with DIG the old ones are read
+// as well and mix(new) - mix(old) is returned (else 0).
+template <int U, bool NT, int T, bool DIG>
+__device__ __forceinline__ uint64_t write_plain(uint8_t* block, const uint8_t* fr,
+                                                const WriteLane& w) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  u32x4 n[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (w.off + u * kStep < w.end) n[u] = ld16<NT>(fr + u * kStep);
+  uint64_t d = 0;
+  if constexpr (DIG) {
+    u32x4 o[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (w.off + u * kStep < w.end) o[u] = ld16<NT>(block + w.off + u * kStep);
+    d = patch_mix<U, T>(n, w.off, w.end, w.z) - patch_mix<U, T>(o, w.off, w.end, w.z);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (w.off + u * kStep < w.end)
+      st16_block<NT, kPatchDataStoreAux>(block, w.off + u * kStep, n[u]);
+  return d;
+}
+
+// One class of one stripe over this lane's granules.  `src` answers which
+// members are written and where this lane's first granule of their new bytes
+// is: src.each(f) calls f(i, fr) for every written member in ascending order
+// (i = its block index in the stripe); src.written(r, fr), called with r
+// ascending from 0, says whether member r (block j + r*m) is written.
+// `x` = the lost written member's block index (rebuild only).
+template <int U, bool NT, int T, bool DIG, typename Src>
+__device__ __forceinline__ void write_tile(uint8_t* data, uint8_t* parity, uint64_t* digests,
+                                           int mode, uint64_t c, uint32_t j, uint32_t x,
+                                           const WriteLane& w, const Geometry& g, Src src) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  uint8_t* par = parity + (c * g.m + j) * g.bs;
+  uint8_t* blocks = data + c * g.k * g.bs;  // the stripe's data blocks
+  uint64_t* row = digests + c * (g.k + g.m);
+  if (mode == kWriteDataOnly) {
+    src.each([&](uint32_t i, const uint8_t* fr) {
+      const uint64_t d = write_plain<U, NT, T, DIG>(blocks + (uint64_t)i * g.bs, fr, w);
+      if constexpr (DIG) patch_wave_add(row + i, d);
+    });
+    return;
+  }
+  u32x4 acc[U];
+  uint64_t psum = 0;
+  if (mode == kWriteDelta) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (w.off + u * kStep < w.end) acc[u] = ld16<NT>(par + w.off + u * kStep);
+    if constexpr (DIG) psum = 0 - patch_mix<U, T>(acc, w.off, w.end, w.z);
+    src.each([&](uint32_t i, const uint8_t* fr) {
+      const uint64_t d = patch_fold<U, NT, T, DIG>(acc, blocks + (uint64_t)i * g.bs, fr, w.off,
+                                                   w.end, w.z);
+      if constexpr (DIG) patch_wave_add(row + i, d);
+    });
+  } else {
+    // rebuild: every member has a source; acc becomes the new parity
+    const uint32_t nm = (uint32_t)g.nm, m = (uint32_t)g.m;
+    u32x4 oldx[U];  // DIG: XOR of the old bytes of every member but x
+    uint64_t dx = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      acc[u] = u32x4{0u, 0u, 0u, 0u};
+      oldx[u] = u32x4{0u, 0u, 0u, 0u};
+    }
+    // member block i with its bytes v loaded from `written ? new : data`
+    auto absorb = [&](uint32_t i, bool written, const u32x4(&v)[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) acc[u] ^= v[u];
+      if (!written) {
+        if constexpr (DIG) {
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            if (w.off + u * kStep < w.end) oldx[u] ^= v[u];
+        }
+        return;
+      }
+      if (i == x) {  // the lost member: its new bytes went into the parity only
+        if constexpr (DIG) dx = patch_mix<U, T>(v, w.off, w.end, w.z);
+        return;
+      }
+      uint8_t* block = blocks + (uint64_t)i * g.bs;
+      if constexpr (DIG) {
+        u32x4 o[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (w.off + u * kStep < w.end) {
+            o[u] = ld16<NT>(block + w.off + u * kStep);
+            oldx[u] ^= o[u];
+          }
+        patch_wave_add(row + i, patch_mix<U, T>(v, w.off, w.end, w.z) -
+                                    patch_mix<U, T>(o, w.off, w.end, w.z));
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end)
+          st16_block<NT, kPatchDataStoreAux>(block, w.off + u * kStep, v[u]);
+    };
+    uint32_t r = 0;
+    // 8 members' loads in flight per granule.  Not with DIG: the 8 granules held
+    // beside the digest arithmetic took the instantiation to 111 VGPRs, and the
+    // delta mode of the same kernel -- every write of a healthy store -- ran
+    // 1.4x xec_update_range's time at 4 waves per SIMD.
+    for (; !DIG && r + 8 <= nm; r += 8) {
+      const uint8_t* from[8];
+      bool wr[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const uint32_t i = j + (r + q) * m;
+        const uint8_t* fr = nullptr;
+        wr[q] = src.written(r + q, fr);
+        from[q] = wr[q] ? fr : blocks + (uint64_t)i * g.bs + w.off;
+      }
+      u32x4 v[8][U];
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (w.off + u * kStep < w.end) v[q][u] = ld16<NT>(from[q] + u * kStep);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) absorb(j + (r + q) * m, wr[q], v[q]);
+    }
+    for (; r < nm; ++r) {
+      const uint32_t i = j + r * m;
+      const uint8_t* fr = nullptr;
+      const bool wr = src.written(r, fr);
+      const uint8_t* from = wr ? fr : blocks + (uint64_t)i * g.bs + w.off;
+      u32x4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) v[u] = ld16<NT>(from + u * kStep);
+      absorb(i, wr, v);
+    }
+    if constexpr (DIG) {
+      u32x4 pold[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) {
+          pold[u] = ld16<NT>(par + w.off + u * kStep);
+          oldx[u] ^= pold[u];  // what block x virtually held
+        }
+      psum = 0 - patch_mix<U, T>(pold, w.off, w.end, w.z);
+      patch_wave_add(row + x, dx - patch_mix<U, T>(oldx, w.off, w.end, w.z));
+    }
+  }
+  if constexpr (DIG) psum += patch_mix<U, T>(acc, w.off, w.end, w.z);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (w.off + u * kStep < w.end)
+      st16_block<NT, kPatchParityStoreAux>(par, w.off + u * kStep, acc[u]);
+  if constexpr (DIG) patch_wave_add(row + g.k + j, psum);
+}
+
+// The written members of class j of stripe c as the ascending list names them,
+// from list position q on; item t's new bytes are at fresh + t*len.
+template <typename At>
+struct ListWritten {
+  At at;
+  uint64_t q, n;
+  uint32_t c, j, m;
+  const uint8_t* fresh;  // + rel: this lane's first granule of item 0
+  uint64_t len;
+
+  template <typename F>
+  __device__ __forceinline__ void each(F f) {
+    for (uint64_t t = q; t < n; ++t) {
+      const uint32_t it = at(t);
+      if ((it >> 8) != c) break;
+      const uint32_t i = it & 0xFFu;
+      if (i % m == j) f(i, fresh + t * len);
+    }
+  }
+  // a merge: members and list both ascend
+  __device__ __forceinline__ bool written(uint32_t r, const uint8_t*& fr) {
+    const uint32_t want = j + r * m;
+    while (q < n) {
+      const uint32_t it = at(q);
+      if ((it >> 8) != c || (it & 0xFFu) >= want) break;
+      ++q;
+    }
+    if (q >= n) return false;
+    const uint32_t it = at(q);
+    if ((it >> 8) != c || (it & 0xFFu) != want) return false;
+    fr = fresh + q * len;
+    ++q;
+    return true;
+  }
+};
+
+// The two loss bits of list position t: bit 0 = this block is lost, bit 1 =
+// this class's parity block is lost (16 items per word).
+template <typename Word>
+__device__ __forceinline__ uint32_t write_bits(Word word_at, uint64_t t) {
+  return (word_at(t >> 4) >> (2u * (uint32_t)(t & 15u))) & 3u;
+}
+
+// List tiles: one per (list position e, chunk of the range), ownership as
+// patch_list_tile; the owner reads the mode off the bits of its class's items.
+template <int U, bool NT, int T, bool DIG, typename At, typename Word>
+__device__ __forceinline__ void write_list_tile(uint8_t* data, uint8_t* parity,
+                                                const uint8_t* __restrict__ fresh,
+                                                uint64_t* digests, uint64_t e, uint64_t n,
+                                                uint64_t chunk, const ReadRange& rr,
+                                                const Geometry& g, At at, Word word_at) {
+  const uint32_t m = (uint32_t)g.m;
+  const uint32_t item = at(e);
+  const uint32_t c = item >> 8, j = (item & 0xFFu) % m;
+  for (uint64_t q = e; q > 0;) {
+    const uint32_t prev = at(--q);
+    if ((prev >> 8) != c) break;
+    if ((prev & 0xFFu) % m == j) return;  // an earlier item's tile handles this one
+  }
+  uint32_t any = 0, x = 0;
+  for (uint64_t q = e; q < n; ++q) {
+    const uint32_t it = at(q);
+    if ((it >> 8) != c) break;
+    if ((it & 0xFFu) % m != j) continue;
+    const uint32_t b = write_bits(word_at, q);
+    any |= b;
+    if (b & 1u) x = it & 0xFFu;
+  }
+  const int mode = (any & 2u) ? kWriteDataOnly : (any & 1u) ? kWriteRebuild : kWriteDelta;
+  const uint64_t rel = (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;  // from the range's start
+  WriteLane w;
+  w.off = rr.offset + rel;
+  w.end = rr.offset + rr.len;
+  w.z = (w.off / 8 + 1) * kSplitmixGolden;
+  write_tile<U, NT, T, DIG>(data, parity, digests, mode, c, j, x, w, g,
+                            ListWritten<At>{at, e, n, c, j, m, fresh + rel, rr.len});
+}
+
+// The list in device memory: n items, then their loss bits (xec_kernels.h).
+template <int U, bool NT, int T, bool DIG>
+__global__ __launch_bounds__(T) void write_list_kernel(uint8_t* data, uint8_t* parity,
+                                                       const uint8_t* __restrict__ fresh,
+                                                       const uint32_t* __restrict__ items,
+                                                       uint64_t* digests, ReadRange rr,
+                                                       Geometry g) {
+  const uint64_t n = g.total_tiles / g.tiles_per_block;
+  const uint32_t* bits = items + n;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as patch_list_kernel
+    write_list_tile<U, NT, T, DIG>(data, parity, fresh, digests, t / g.tiles_per_block, n,
+                                   t % g.tiles_per_block, rr, g,
+                                   [&](uint64_t q) { return *(const_u32_as4)(items + q); },
+                                   [&](uint64_t q) { return *(const_u32_as4)(bits + q); });
+  }
+}
+
+// The same with items and bits in the kernel arguments (at most CAP items).
+template <int U, bool NT, int T, bool DIG, uint32_t CAP>
+__global__ __launch_bounds__(T) void write_arglist_kernel(uint8_t* data, uint8_t* parity,
+                                                          const uint8_t* __restrict__ fresh,
+                                                          uint64_t* digests, ReadRange rr,
+                                                          Geometry g, ArgItems<CAP> items,
+                                                          ArgItems<CAP / 16> bits) {
+  const uint64_t n = g.total_tiles / g.tiles_per_block;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    write_list_tile<U, NT, T, DIG>(data, parity, fresh, digests, t / g.tiles_per_block, n,
+                                   t % g.tiles_per_block, rr, g,
+                                   [&](uint64_t q) { return items.v[q]; },
+                                   [&](uint64_t q) { return bits.v[q]; });
+  }
+}
+
+// The written members of a class as the device mask marks them; fresh mirrors
+// data, `first` = this lane's first granule in the class's member 0.
+struct MaskWritten {
+  uint64_t mrow;  // address of the mask byte of member 0
+  uint32_t nm, j, m;
+  const uint8_t* first;
+  uint64_t stride;
+
+  template <typename F>
+  __device__ __forceinline__ void each(F f) {
+    for (uint32_t r = 0; r < nm; ++r)
+      if (sbyte(mrow + (uint64_t)r * m) != 0) f(j + r * m, first + r * stride);
+  }
+  __device__ __forceinline__ bool written(uint32_t r, const uint8_t*& fr) {
+    if (sbyte(mrow + (uint64_t)r * m) == 0) return false;
+    fr = first + r * stride;
+    return true;
+  }
+};
+
+// Class tiles over a device mask and bitmap (xec_write_device), gated on
+// write_check_kernel's verdict: (stripe, class, chunk of the range).  A class
+// without a marked member is skipped after its mask bytes; bitmap == nullptr
+// means everything is present.
+template <int U, bool NT, int T, bool DIG>
+__global__ __launch_bounds__(T) void write_class_kernel(uint8_t* data, uint8_t* parity,
+                                                        const uint8_t* __restrict__ fresh,
+                                                        const uint8_t* __restrict__ mask,
+                                                        const uint8_t* __restrict__ bitmap,
+                                                        uint64_t* digests, ReadRange rr,
+                                                        Geometry g) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  const uint32_t nm = (uint32_t)g.nm, m = (uint32_t)g.m;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as patch_class_kernel
+    const TileCoord tc = tile_coord(t, g);
+    const uint32_t j = (uint32_t)tc.j;
+    const uint64_t mrow = reinterpret_cast<uint64_t>(mask + tc.c * g.k) + j;
+    const uint64_t brow = reinterpret_cast<uint64_t>(bitmap) + tc.c * (g.k + g.m);
+    bool any = false, lost = false;
+    uint32_t x = 0;
+    for (uint32_t r = 0; r < nm; ++r) {
+      if (sbyte(mrow + (uint64_t)r * m) == 0) continue;
+      any = true;
+      if (bitmap != nullptr && sbyte(brow + j + (uint64_t)r * m) == 0) {
+        lost = true;
+        x = j + r * m;
+      }
+    }
+    if (!any) continue;
+    const bool plost = bitmap != nullptr && sbyte(brow + g.k + j) == 0;
+    const int mode = plost ? kWriteDataOnly : lost ? kWriteRebuild : kWriteDelta;
+    WriteLane w;
+    w.off = rr.offset + (tc.chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+    w.end = rr.offset + rr.len;
+    w.z = (w.off / 8 + 1) * kSplitmixGolden;
+    write_tile<U, NT, T, DIG>(data, parity, digests, mode, tc.c, j, x, w, g,
+                              MaskWritten{mrow, nm, j, m,
+                                          fresh + (tc.c * g.k + j) * g.bs + w.off, m * g.bs});
+  }
+}
+
+// One thread per (stripe, class): *status = 4 if a marked member of the class
+// is lost while another block of the class (a member or the parity) is lost.
+__global__ __launch_bounds__(256) void write_check_kernel(const uint8_t* __restrict__ bitmap,
+                                                         const uint8_t* __restrict__ mask,
+                                                         Geometry g, int32_t* status) {
+  const uint64_t row = g.k + g.m, n = g.S * g.m;
+  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n;
+       t += (uint64_t)gridDim.x * 256) {
+    const uint64_t c = t / g.m, j = t % g.m;
+    const uint8_t* b = bitmap + c * row;
+    const uint8_t* mk = mask + c * g.k;
+    uint32_t lost = b[g.k + j] == 0, marked_lost = 0;
+    for (uint64_t l = j; l < g.k; l += g.m) {
+      if (b[l] != 0) continue;
+      ++lost;
+      marked_lost |= mk[l] != 0;
+    }
+    if (marked_lost != 0 && lost > 1) atomicMax(status, 4 /* XEC_DECODE_FAILURE */);
+  }
+}
+
+namespace {
+
+template <int U, bool NT, int T, bool DIG>
+hipError_t launch_write_t(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
+                          const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
+                          int tiling, uint32_t grid, uint32_t lds, hipStream_t s,
+                          const ArgList& al, const uint32_t* h_bits) {
+  if (tiling == kUpdateArgListTiles) {
+    const uint64_t words = (al.n + 15) / 16;
+    switch (arg_items_capacity(al.n)) {
+      case 64:
+        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 64>, grid, T, lds, s, d, p, fresh,
+                            dig, rr, g, arg_items<64>(al.items, al.n), arg_items<4>(h_bits, words));
+      case 256:
+        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 256>, grid, T, lds, s, d, p, fresh,
+                            dig, rr, g, arg_items<256>(al.items, al.n),
+                            arg_items<16>(h_bits, words));
+      default:
+        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 1024>, grid, T, lds, s, d, p,
+                            fresh, dig, rr, g, arg_items<1024>(al.items, al.n),
+                            arg_items<64>(h_bits, words));
+    }
+  }
+  if (tiling == kUpdateListTiles)
+    return launch_codec(write_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
+                        static_cast<const uint32_t*>(sel), dig, rr, g);
+  return launch_codec(write_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
+                      static_cast<const uint8_t*>(sel), bm, dig, rr, g);
+}
+
+template <bool NT, int T, bool DIG>
+hipError_t write_u(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
+                   const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
+                   int tiling, int unroll, uint32_t grid, uint32_t lds, hipStream_t s,
+                   const ArgList& a, const uint32_t* h_bits) {
+  return unroll == 2 ? launch_write_t<2, NT, T, DIG>(d, p, fresh, sel, bm, dig, rr, g, tiling, grid,
+                                                     lds, s, a, h_bits)
+                     : launch_write_t<1, NT, T, DIG>(d, p, fresh, sel, bm, dig, rr, g, tiling, grid,
+                                                     lds, s, a, h_bits);
+}
+
+template <bool NT, int T>
+hipError_t write_dig(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
+                     const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
+                     int tiling, int unroll, uint32_t grid, uint32_t lds, hipStream_t s,
+                     const ArgList& a, const uint32_t* h_bits) {
+  return dig != nullptr ? write_u<NT, T, true>(d, p, fresh, sel, bm, dig, rr, g, tiling, unroll,
+                                               grid, lds, s, a, h_bits)
+                        : write_u<NT, T, false>(d, p, fresh, sel, bm, dig, rr, g, tiling, unroll,
+                                                grid, lds, s, a, h_bits);
+}
+
+}  // namespace
+
+hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
+                        const uint8_t* d_bitmap, uint64_t* d_digests, const Geometry& g_class,
+                        const LaunchShape& ls, int tiling, uint64_t offset, uint64_t len,
+                        hipStream_t s, uint64_t n_items, const uint32_t* h_items,
+                        const uint32_t* h_bits) {
+  if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs ||
+      tiling < kUpdateClassTiles || tiling > kUpdateArgListTiles)
+    return hipErrorInvalidValue;
+  Geometry g = g_class;
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
+  g.total_tiles = (tiling == kUpdateClassTiles ? g.S * g.m : n_items) * g.tiles_per_block;
+  g.rot = 0;
+  if (g.total_tiles == 0) return hipSuccess;
+  if (g.k > 256 && tiling != kUpdateClassTiles) return hipErrorInvalidValue;
+  if (tiling == kUpdateArgListTiles &&
+      (n_items > kArgItems || h_items == nullptr || h_bits == nullptr))
+    return hipErrorInvalidValue;
+  if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
+  if (tiling == kUpdateClassTiles && g.gate == nullptr) return hipErrorInvalidValue;
+  const ReadRange rr{offset, len};
+  const ArgList a{h_items, n_items};
+  uint8_t* d = static_cast<uint8_t*>(d_data);
+  uint8_t* p = static_cast<uint8_t*>(d_parity);
+  const uint8_t* f = static_cast<const uint8_t*>(d_new);
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  if (ls.threads == 256)
+    return ls.nt ? write_dig<true, 256>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
+                                        ls.unroll, grid, lds, s, a, h_bits)
+                 : write_dig<false, 256>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
+                                         ls.unroll, grid, lds, s, a, h_bits);
+  return ls.nt ? write_dig<true, 64>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling, ls.unroll,
+                                     grid, lds, s, a, h_bits)
+               : write_dig<false, 64>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
+                                      ls.unroll, grid, lds, s, a, h_bits);
+}
+
+hipError_t launch_write_check(const uint8_t* d_bitmap, const uint8_t* d_mask, const Geometry& g,
+                              int32_t* d_status, hipStream_t s) {
+  const uint64_t n = g.S * g.m;
+  if (n == 0 || d_bitmap == nullptr) return hipSuccess;
+  return launch(write_check_kernel, grid_for((n + 255) / 256, 8192, 256), 256, 0, s, d_bitmap,
+                d_mask, g, d_status);
+}
+
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set
 // is told once, on stderr, that every launch of the library will fail
 // (a silent hook in the shipped library).

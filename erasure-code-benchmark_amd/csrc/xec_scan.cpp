@@ -434,6 +434,55 @@ extern "C" xec_status xec_check_read_items(const uint8_t* bm, size_t S, size_t k
   return xec_scan_read_items(bm, S, k, m, items, n_items, nullptr, n_lost);
 }
 
+// ---- write scan (xec_write, xec_check_write_items) ------------------------------
+// The read scan's rule over written items (data blocks only, strictly
+// ascending), with two bits out per item.  A broken item rule anywhere in the
+// list outranks an unservable item, so the walk goes on after the first failure.
+xec_status xec_scan_write_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                                const uint32_t* items, size_t n_items, uint32_t* bits,
+                                size_t* n_rebuild, size_t* n_data_only) {
+  if (n_rebuild) *n_rebuild = 0;
+  if (n_data_only) *n_data_only = 0;
+  if (k < 1 || m < 1 || k % m != 0) return XEC_INVALID_COUNTS;
+  if (items == nullptr && n_items != 0) return XEC_INVALID_COUNTS;
+  const size_t row = k + m;
+  if (bits != nullptr)
+    for (size_t w = 0; w < (n_items + 15) / 16; ++w) bits[w] = 0;
+  size_t rebuild = 0, data_only = 0;
+  bool failed = false;
+  for (size_t t = 0; t < n_items; ++t) {
+    const size_t c = items[t] >> 8, i = items[t] & 0xFFu;
+    if (c >= S || i >= k || (t > 0 && items[t] <= items[t - 1])) return XEC_INVALID_COUNTS;
+    if (bm == nullptr || failed) continue;  // after a failure only the item rules matter
+    const uint8_t* r = bm + c * row;
+    const size_t j = i % m;
+    const bool parity_lost = r[k + j] == 0;
+    uint32_t b = parity_lost ? 2u : 0u;
+    if (r[i] == 0) {
+      bool alone = !parity_lost;
+      for (size_t l = j; l < k && alone; l += m) alone = l == i || r[l] != 0;
+      if (!alone) {
+        failed = true;
+        continue;
+      }
+      b |= 1u;
+      ++rebuild;
+    }
+    if (parity_lost) ++data_only;
+    if (bits != nullptr) bits[t >> 4] |= b << (2 * (t & 15));
+  }
+  if (failed) return XEC_DECODE_FAILURE;
+  if (n_rebuild) *n_rebuild = rebuild;
+  if (n_data_only) *n_data_only = data_only;
+  return XEC_SUCCESS;
+}
+
+extern "C" xec_status xec_check_write_items(const uint8_t* bm, size_t S, size_t k, size_t m,
+                                            const uint32_t* items, size_t n_items,
+                                            size_t* n_rebuild, size_t* n_data_only) {
+  return xec_scan_write_items(bm, S, k, m, items, n_items, nullptr, n_rebuild, n_data_only);
+}
+
 namespace {
 
 void loss_masks_scalar(const uint8_t* bm, size_t S, size_t k, size_t m, uint32_t* masks) {

@@ -16,7 +16,9 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     set_rotation, set_validate_kernel,
                     status_string, update, update_device, update_scratch_bytes,
                     update_tiling_used, validate_blocks, verify, write_validation_pattern,
-                    digest_range_host, update_range, update_range_device)
+                    digest_range_host, update_range, update_range_device,
+                    check_write_items, write, write_device, write_scratch_bytes,
+                    write_tiling_used)
 from .partition import stripe_range
 
 __all__ = [
@@ -34,4 +36,5 @@ __all__ = [
     "update", "update_device", "update_scratch_bytes", "update_tiling_used", "validate_blocks",
     "verify", "write_validation_pattern",
     "digest_range_host", "update_range", "update_range_device",
+    "check_write_items", "write", "write_device", "write_scratch_bytes", "write_tiling_used",
 ]

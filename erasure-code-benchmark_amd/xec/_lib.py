@@ -36,6 +36,8 @@ EXPORTED = (
     "xec_read", "xec_read_scratch_bytes", "xec_read_device", "xec_check_read_items",
     "xec_read_tiling_used",
     "xec_update_range", "xec_update_range_device", "xec_digest_range_host",
+    "xec_write", "xec_write_scratch_bytes", "xec_write_device", "xec_check_write_items",
+    "xec_write_tiling_used",
 )
 
 
@@ -134,6 +136,12 @@ def lib() -> ctypes.CDLL:
         "xec_update_range": ([vp, vp, vp, sz, sz, sz, sz, vp, sz, sz, sz, vp, vp, sz, vp], st),
         "xec_update_range_device": ([vp, vp, vp, sz, sz, sz, sz, vp, sz, sz, vp, vp], st),
         "xec_digest_range_host": ([vp, sz, sz], ctypes.c_uint64),
+        "xec_write": ([vp, vp, vp, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, sz, vp], st),
+        "xec_write_scratch_bytes": ([sz], sz),
+        "xec_write_device": ([vp, vp, vp, sz, sz, sz, sz, vp, vp, sz, sz, vp, vp, vp], st),
+        "xec_check_write_items": ([vp, sz, sz, sz, vp, sz, ctypes.POINTER(sz),
+                                   ctypes.POINTER(sz)], st),
+        "xec_write_tiling_used": ([], ctypes.c_int),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

@@ -190,6 +190,59 @@ def update_range_device(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int
                                                 _ptr(d_digests), _stream(stream)))
 
 
+def write(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, h_bitmap, h_items,
+          n_items: int, offset: int, length: int, d_digests=None, d_scratch=None,
+          scratch_bytes: int = 0, stream=None) -> Status:
+    """xec_write -- xec_update_range under a loss bitmap (h_bitmap byte 0 = lost;
+    None = all present): a lost block is never read and never written.  A class
+    whose parity is lost takes the new bytes only; a lost written block's bytes
+    go into its class's parity, recomputed over the range, for a later repair to
+    reconstruct.  An item that is lost with another block of its class lost is
+    DECODE_FAILURE and nothing changes.  d_scratch (write_scratch_bytes(n_items)
+    device bytes) is needed only past 1,024 items."""
+    return Status(lib().xec_write(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs, k, m,
+                                  _ptr(h_bitmap) if h_bitmap is not None else None,
+                                  _ptr(h_items) if h_items is not None else None, n_items,
+                                  offset, length, _ptr(d_digests), _ptr(d_scratch), scratch_bytes,
+                                  _stream(stream)))
+
+
+def write_device(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, d_bitmap, d_mask,
+                 offset: int, length: int, d_digests, d_status, stream=None) -> Status:
+    """xec_write_device -- the same with bitmap (None = all present) and mask on
+    the device and d_new a shadow of d_data's layout; the verdict lands in
+    d_status (int32 device tensor: 0, or 4 a marked block not servable) in
+    stream order; capturable."""
+    return Status(lib().xec_write_device(_ptr(d_data), _ptr(d_parity), _ptr(d_new), S, bs, k, m,
+                                         _ptr(d_bitmap) if d_bitmap is not None else None,
+                                         _ptr(d_mask), offset, length, _ptr(d_digests),
+                                         _ptr(d_status), _stream(stream)))
+
+
+def write_scratch_bytes(n_items: int) -> int:
+    """xec_write_scratch_bytes: 4 * (n_items + ceil(n_items / 16))."""
+    return int(lib().xec_write_scratch_bytes(n_items))
+
+
+def check_write_items(h_bitmap, S: int, k: int, m: int, h_items,
+                      n_items: int) -> tuple[Status, int, int]:
+    """xec_check_write_items -- the host scan xec_write runs (no GPU, no init):
+    (status, items that are lost, items whose class lost its parity)."""
+    n_rebuild, n_data_only = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = Status(lib().xec_check_write_items(_ptr(h_bitmap) if h_bitmap is not None else None,
+                                            S, k, m,
+                                            _ptr(h_items) if h_items is not None else None,
+                                            n_items, ctypes.byref(n_rebuild),
+                                            ctypes.byref(n_data_only)))
+    return st, int(n_rebuild.value), int(n_data_only.value)
+
+
+def write_tiling_used() -> int:
+    """xec_write_tiling_used: the tiling this thread's last write launched (0 none,
+    2 class tiles, 3 list in d_scratch, 4 list in the kernel arguments)."""
+    return int(lib().xec_write_tiling_used())
+
+
 def digest(d_data, d_parity, S: int, bs: int, k: int, m: int, d_digests, d_select=None,
            stream=None) -> Status:
     """xec_digest -- d_digests (S*(k+m) device uint64, the bitmap's layout) =

@@ -581,6 +581,129 @@ xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_n
                                    size_t offset, size_t len, uint64_t* d_digests,
                                    hipStream_t stream);
 
+/* Degraded write (no reference counterpart): xec_update_range under a loss
+ * bitmap, the write-side counterpart of xec_read.  It follows xec_read's rule:
+ * a lost block (bitmap byte 0) is never read and never written.  Items, range,
+ * d_new's packing and d_digests are xec_update_range's: h_items[t] = c << 8 | i,
+ * i < k, strictly ascending; one range [offset, offset + len) per call,
+ * multiples of 16; item t's new bytes at d_new + t*len; d_digests may be NULL.
+ * h_bitmap == NULL means everything is present, and the call then leaves
+ * exactly the bytes and digest slots xec_update_range leaves.
+ *
+ * Every (stripe, class) with at least one item runs in one of three modes; W is
+ * the set of its written members, its blocks are its k/m data members and its
+ * parity block.
+ *  - Delta: the parity block is present and no member of W is lost.
+ *    parity[range] ^= old ^ new per written member and data[range] = new,
+ *    exactly as xec_update_range: 3*len read and 2*len written per item.  A
+ *    lost member that is NOT written is not touched -- the delta never needs
+ *    it.  The class's syndrome is kept.
+ *  - Data-only: the parity block is lost.  Each written (present) member takes
+ *    its new bytes; parity is neither read nor written, and a later xec_repair
+ *    re-encodes it.  len read (the new bytes) and len written per item; with
+ *    d_digests the old range is read as well.
+ *  - Rebuild-write: one member x of W is lost and every other block of the
+ *    class is present.
+ *        parity[range] = new_x ^ XOR_{r != x} (new_r if r in W else data_r)[range]
+ *    Present written members take their new bytes; block x is not touched.
+ *    Outside the range nothing changes, so the bytes a later xec_repair
+ *    reconstructs for x are its old (virtual) bytes outside the range and new_x
+ *    inside it.  Old parity is read only with d_digests.  The parity's range is
+ *    RECOMPUTED, so a syndrome the class carried inside the range is gone: this
+ *    is the one mode that cannot keep it (outside the range it stays).
+ *
+ * Servability is xec_read's rule over the written items: an item is servable if
+ * its block is present, or if it is lost and every other block of its class is
+ * present.  All-or-nothing over the requested items: one unservable item gives
+ * XEC_DECODE_FAILURE, nothing is queued and nothing changes.  As with xec_read,
+ * blocks of other classes and other stripes play no part: a batch xec_repair
+ * refuses still takes every write that does not target a LOST block of a
+ * doubly-lost class -- with a data member and the parity both lost, a write to
+ * a third, present member runs data-only.
+ *
+ * Digest upkeep (d_digests != NULL, xec_digest's layout).  Delta: as
+ * xec_update_range.  Data-only: each written block's slot gets
+ * += mix(new) - mix(old) over the range; the lost parity block's slot is
+ * neither read nor written and is STALE after the repair: refresh it with
+ * xec_digest(select) then.  Rebuild-write: written present blocks as data-only;
+ * the lost block x gets += mix(new_x) - mix(P_old ^ XOR_{r != x} old_r), the
+ * difference against the bytes it virtually held; the parity slot gets
+ * += mix(P_new) - mix(P_old).  So with slots that held the digests of the
+ * blocks before the loss, xec_write and then xec_repair under the same bitmap
+ * leave a full xec_locate counting exactly the parity blocks of the data-only
+ * classes, and none once those are refreshed.  xec_update_range's caveat
+ * carries over: damaged old bytes inside the range move into parity (delta) or
+ * stay in the slot.
+ *
+ * Checks, all on the host before anything is queued, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. xec_check_args;
+ *  3. n_items == 0 or S == 0 -> XEC_SUCCESS, nothing queued;
+ *  4. k > 256 or S > 2^24 -> XEC_INVALID_SIZE (the packing);
+ *  5. to 8. steps 5 to 8 of xec_update_range (the range; d_new or h_items NULL;
+ *     the alignments; the overlaps);
+ *  9. the item rules of xec_update -> XEC_INVALID_COUNTS (anywhere in the list:
+ *     it outranks step 10);
+ * 10. an item that is not servable -> XEC_DECODE_FAILURE;
+ * 11. more than 1,024 items: d_scratch not 4-byte aligned ->
+ *     XEC_INVALID_ALIGNMENT; NULL or fewer than xec_write_scratch_bytes(n_items)
+ *     bytes -> XEC_INVALID_SIZE.
+ * A rejected call queues nothing and changes nothing.  The host scan attaches
+ * two bits to each item -- "this block is lost", "this class's parity is lost"
+ * -- and the tile that owns the class derives the mode from the bits of its
+ * items.  Up to 1,024 items and their bits travel in the kernel arguments
+ * (capacities 64 / 256 / 1024); a longer list is staged in pinned memory, items
+ * then bits, and uploaded into d_scratch in one copy on `stream`.  h_bitmap and
+ * h_items are read before the call returns.  Not capturable, as xec_update: on
+ * a capturing stream a call with work returns XEC_DEVICE_ERROR with nothing
+ * queued.  One kernel over (list position, chunk of the range) tiles; of
+ * xec_set_launch all four arguments apply, xec_set_rotation does not; residency
+ * is uncapped. */
+xec_status xec_write(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                     size_t k, size_t m, const uint8_t* h_bitmap, const uint32_t* h_items,
+                     size_t n_items, size_t offset, size_t len, uint64_t* d_digests,
+                     void* d_scratch, size_t scratch_bytes, hipStream_t stream);
+
+/* Scratch bytes xec_write needs for a list of n_items: 4 * (n_items +
+ * ceil(n_items / 16)), the items and two bits each.  Needed only past 1,024
+ * items. */
+size_t xec_write_scratch_bytes(size_t n_items);
+
+/* Device-resident form of xec_write: nothing happens on the host, so it can be
+ * captured in a hipGraph, and there is no limit on k or S.  d_mask and the
+ * shadow d_new are xec_update_range_device's; d_bitmap is S*(k+m) device bytes
+ * (0 = lost) or NULL for all present.  Enqueues on `stream`: *d_status = 0 (a
+ * memset, as xec_read_device); a check kernel that sets *d_status = 4 if any
+ * marked block is lost while another block of its class is lost (not launched
+ * with d_bitmap NULL); then the write kernel over (stripe, class, chunk of the
+ * range) tiles, which does nothing if *d_status != 0 and otherwise reads each
+ * class's mask and bitmap bytes and picks its mode.
+ * Checks: 1, 2, S == 0 -> XEC_SUCCESS with nothing queued, then the checks of
+ * xec_update_range_device, then d_status NULL or not 4-byte aligned ->
+ * XEC_INVALID_ALIGNMENT. */
+xec_status xec_write_device(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
+                            size_t k, size_t m, const uint8_t* d_bitmap, const uint8_t* d_mask,
+                            size_t offset, size_t len, uint64_t* d_digests, int32_t* d_status,
+                            hipStream_t stream);
+
+/* Host-only scan xec_write runs over its items (no GPU and no xec_init needed):
+ * XEC_INVALID_COUNTS if an item breaks xec_update's rules (i >= k, c >= S, not
+ * strictly ascending; or k, m are invalid as in xec_check_args, or h_items is
+ * NULL with n_items > 0) anywhere in the list, else XEC_DECODE_FAILURE if an
+ * item is not servable, else XEC_SUCCESS with *n_rebuild = the lost items
+ * (rebuild-write) and *n_data_only = the items whose class lost its parity
+ * block -- items, not classes; either pointer may be NULL.  h_bitmap == NULL:
+ * everything is present. */
+xec_status xec_check_write_items(const uint8_t* h_bitmap, size_t S, size_t k, size_t m,
+                                 const uint32_t* h_items, size_t n_items, size_t* n_rebuild,
+                                 size_t* n_data_only);
+
+/* Diagnostics: which tiling the calling thread's most recent xec_write or
+ * xec_write_device launched -- 0 none (an error, or nothing to write),
+ * XEC_TILING_ARG_LIST or XEC_TILING_LIST (xec_write), XEC_TILING_CLASS
+ * (xec_write_device).  The other *_tiling_used values are not affected. */
+int xec_write_tiling_used(void);
+
 /* The digest terms of a range: the sum over the len/8 little-endian words w[n]
  * at `bytes` of splitmix_at(w[n], offset/8 + n)  (mod 2^64) -- `bytes` points
  * at the range's first byte, `offset` is where that byte sits in its block.
@@ -659,8 +782,8 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * k/m at the default launch shape -- 1 at k/m = 32, 2 at 16, 4 at 4 and 8;
  * for other member counts none below 8, 4 below 20, 2 below 56, else 1;
  * none at 1 and 2.  The repair kernels take the same table;
- * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels and
- * the digest kernel run uncapped at every k/m (their own sweeps); the read
+ * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels, the
+ * write kernels and the digest kernel run uncapped at every k/m (their own sweeps); the read
  * kernel takes the table, except that an xec_read whose items are all present
  * runs uncapped.  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
@@ -704,8 +827,8 @@ xec_status xec_set_validate_kernel(int mode);
  * so results are identical; it changes which columns of the stripes in flight
  * together are read at once.  0 = automatic (the measured default), -1 = none,
  * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
- * It does not apply to xec_read / xec_read_device and xec_update_range /
- * xec_update_range_device: their tiles walk the chunks of each item's byte
+ * It does not apply to xec_read / xec_read_device, xec_update_range /
+ * xec_update_range_device and xec_write / xec_write_device: their tiles walk the chunks of each item's byte
  * range, not a column of every stripe. */
 xec_status xec_set_rotation(int tiles);
 
@@ -747,9 +870,9 @@ int xec_decode_arg_capacity_used(void);
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
- * xec_digest, xec_locate, xec_read, xec_read_device, xec_update_range or
- * xec_update_range_device call
- * launches its encode / decode / repair / verify / update / digest / read kernel with hipExtLaunchKernel and these two
+ * xec_digest, xec_locate, xec_read, xec_read_device, xec_update_range,
+ * xec_update_range_device, xec_write or xec_write_device call
+ * launches its encode / decode / repair / verify / update / digest / read / write kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
  * time, with no event packet queued between kernels (a hipEventRecord between
