@@ -593,6 +593,84 @@ uint32_t resident_workgroups(const xec::LaunchShape& ls) {
   return (uint32_t)cus * (per_cu ? per_cu : 1u);
 }
 
+// xec_set_kernel_events arms the next codec call of this thread; that call
+// consumes the setting whether or not it launched a kernel (include/xec.h).
+struct KernelEventsScope {
+  ~KernelEventsScope() { xec::t_kernel_events = xec::KernelEvents{}; }
+};
+
+// The body of a codec entry point whose host-side bookkeeping allocates (upload
+// buffers, pinned staging, their lists).  No exception crosses the C ABI: an
+// allocation failure there is a device error for the caller, not a
+// std::terminate.
+template <class Body>
+xec_status guarded(Body&& body) {
+  const KernelEventsScope events_scope;
+  try {
+    return body();
+  } catch (...) {
+    return XEC_DEVICE_ERROR;
+  }
+}
+
+// XEC_DEBUG=1: a call that fails with XEC_DEVICE_ERROR names its line, the
+// HIP error of the failing call and the one pending on the thread (stderr;
+// diagnostics only).
+bool debug_on() {
+  static const bool on = [] {
+    const char* e = std::getenv("XEC_DEBUG");
+    return e != nullptr && e[0] == '1';
+  }();
+  return on;
+}
+xec_status dev_error(int line, hipError_t e) {
+  if (debug_on())
+    std::fprintf(stderr, "xec: device error at xec_api.cpp:%d (%s; pending %s)\n", line,
+                 hipGetErrorName(e), hipGetErrorName(hipPeekAtLastError()));
+  return XEC_DEVICE_ERROR;
+}
+#define DEVERR(e) dev_error(__LINE__, (e))
+// What a launch returned, as the ABI's status; `line` is the entry point's own.
+xec_status launch_status(int line, hipError_t le) {
+  return le == hipSuccess ? XEC_SUCCESS : dev_error(line, le);
+}
+
+// The device scratch a list too long for the kernel arguments goes through.
+xec_status check_scratch(const void* d_scratch, size_t scratch_bytes, size_t need) {
+  if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+  if (d_scratch == nullptr || scratch_bytes < need) return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+// Items c << 8 | i of data blocks: each in range, and strictly ascending =
+// batch order, no duplicates.
+bool items_ascending(const uint32_t* h_items, size_t n, size_t S, size_t k) {
+  for (size_t t = 0; t < n; ++t) {
+    const uint32_t it = h_items[t];
+    if ((it & 0xFFu) >= k || (it >> 8) >= S || (t > 0 && it <= h_items[t - 1])) return false;
+  }
+  return true;
+}
+
+// A list too long for the kernel arguments: fill(words) writes its `bytes` into
+// pinned staging, one copy on `stream` itself takes them to d_scratch, and
+// launch() queues the kernel that reads them there.  `line`: see launch_status.
+template <class Fill, class Launch>
+xec_status upload_list_and_launch(size_t bytes, void* d_scratch, hipStream_t stream, int line,
+                                  Fill&& fill, Launch&& launch) {
+  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
+  if (!sd.ok()) return dev_error(line, hipSuccess);
+  bool fault = false;
+  Staging* sg = stage_acquire(bytes, sd.device(), &fault);
+  if (sg == nullptr) return dev_error(line, hipSuccess);
+  fill(static_cast<uint32_t*>(sg->host));
+  hipError_t le = hipMemcpyAsync(d_scratch, sg->host, bytes, hipMemcpyHostToDevice, stream);
+  const bool queued = le == hipSuccess;
+  if (queued) le = launch();
+  stage_release(sg, queued, stream, false);
+  return launch_status(line, le);
+}
+
 }  // namespace
 
 extern "C" {
@@ -604,6 +682,13 @@ xec_status xec_check_args(const void* data, const void* parity, size_t bs, size_
   if (bs < kMinBlock || bs % kBlockMultiple != 0) return XEC_INVALID_SIZE;
   if (k < 1 || m < 1 || k % m != 0) return XEC_INVALID_COUNTS;
   return XEC_SUCCESS;
+}
+
+// What every entry point that takes a batch checks first, in this order.
+static xec_status check_entry(const void* data, const void* parity, size_t bs, size_t k,
+                              size_t m) {
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  return xec_check_args(data, parity, bs, k, m);
 }
 
 // xec_check_bitmap / xec_scan_bitmap live in xec_scan.cpp (host-only, AVX2 where available).
@@ -620,12 +705,6 @@ xec_status xec_init(int device_id) {
   return XEC_SUCCESS;
 }
 
-// xec_set_kernel_events arms the next codec call of this thread; that call
-// consumes the setting whether or not it launched a kernel (include/xec.h).
-struct KernelEventsScope {
-  ~KernelEventsScope() { xec::t_kernel_events = xec::KernelEvents{}; }
-};
-
 xec_status xec_set_kernel_events(hipEvent_t start, hipEvent_t stop) {
   xec::t_kernel_events = xec::KernelEvents{start, stop};
   return XEC_SUCCESS;
@@ -634,8 +713,7 @@ xec_status xec_set_kernel_events(hipEvent_t start, hipEvent_t stop) {
 xec_status xec_encode(const void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                       hipStream_t stream) {
   const KernelEventsScope events_scope;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   const xec::LaunchShape ls = launch_shape(bs, auto_occupancy(k / m));
@@ -660,31 +738,12 @@ constexpr size_t kCopyFirstBitmapBytes = 256u << 10;
 // against the better of them, profiles/r02n/tiling_uniform.json, r02o).
 constexpr uint64_t kListStripesNum = 3, kListStripesDen = 4;
 
-// XEC_DEBUG=1: a decode that fails with XEC_DEVICE_ERROR names its line, the
-// HIP error of the failing call and the one pending on the thread (stderr;
-// diagnostics only).
-static bool debug_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("XEC_DEBUG");
-    return e != nullptr && e[0] == '1';
-  }();
-  return on;
-}
-static xec_status dev_error(int line, hipError_t e) {
-  if (debug_on())
-    std::fprintf(stderr, "xec: device error at xec_api.cpp:%d (%s; pending %s)\n", line,
-                 hipGetErrorName(e), hipGetErrorName(hipPeekAtLastError()));
-  return XEC_DEVICE_ERROR;
-}
-#define DEVERR(e) dev_error(__LINE__, (e))
-
 static xec_status decode_impl(void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                               size_t m, const uint8_t* h_bitmap, uint8_t* d_bitmap,
                               hipStream_t stream) {
   g_tiling_used = 0;
   g_arg_cap_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   const size_t bitmap_bytes = S * (k + m);
@@ -877,17 +936,10 @@ static xec_status decode_impl(void* d_data, const void* d_parity, size_t S, size
   return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
 }
 
-// No exception crosses the C ABI: the host-side bookkeeping allocates (upload
-// buffers, pinned staging, their lists), and an allocation failure there is a
-// device error for the caller, not a std::terminate.
 xec_status xec_decode(void* d_data, const void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                       const uint8_t* h_bitmap, uint8_t* d_bitmap, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {
-    return decode_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  return guarded(
+      [&] { return decode_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, stream); });
 }
 
 int xec_decode_tiling_used(void) { return g_tiling_used; }
@@ -898,8 +950,7 @@ static xec_status decode_per_stripe_impl(void* d_data, const void* d_parity, siz
                                          uint8_t* d_bitmap, uint8_t* h_codes, hipStream_t stream) {
   g_tiling_used = 0;
   g_arg_cap_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
@@ -975,21 +1026,17 @@ static xec_status decode_per_stripe_impl(void* d_data, const void* d_parity, siz
 xec_status xec_decode_per_stripe(void* d_data, const void* d_parity, size_t S, size_t bs,
                                  size_t k, size_t m, const uint8_t* h_bitmap, uint8_t* d_bitmap,
                                  uint8_t* h_codes, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
+  return guarded([&] {
     return decode_per_stripe_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, h_codes,
                                   stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  });
 }
 
 xec_status xec_decode_device(void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                              size_t m, const uint8_t* d_bitmap, int32_t* d_status,
                              hipStream_t stream) {
   const KernelEventsScope events_scope;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   // every argument is checked before any work is queued on the stream
   if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
@@ -1021,8 +1068,7 @@ xec_status xec_decode_device_list(void* d_data, const void* d_parity, size_t S, 
                                   size_t k, size_t m, const uint8_t* d_bitmap, void* d_work,
                                   size_t work_bytes, int32_t* d_status, hipStream_t stream) {
   const KernelEventsScope events_scope;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   // every argument is checked before any work is queued on the stream
   if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0 ||
@@ -1078,8 +1124,7 @@ static xec_status repair_impl(void* d_data, void* d_parity, size_t S, size_t bs,
                               size_t m, const uint8_t* h_bitmap, uint8_t* d_bitmap,
                               hipStream_t stream) {
   g_repair_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
@@ -1124,12 +1169,8 @@ static xec_status repair_impl(void* d_data, void* d_parity, size_t S, size_t bs,
 
 xec_status xec_repair(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                       const uint8_t* h_bitmap, uint8_t* d_bitmap, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
-    return repair_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  return guarded(
+      [&] { return repair_impl(d_data, d_parity, S, bs, k, m, h_bitmap, d_bitmap, stream); });
 }
 
 int xec_repair_tiling_used(void) { return g_repair_tiling_used; }
@@ -1139,8 +1180,7 @@ xec_status xec_repair_device(void* d_data, void* d_parity, size_t S, size_t bs, 
                              hipStream_t stream) {
   const KernelEventsScope events_scope;
   g_repair_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   // every argument is checked before any work is queued on the stream
   if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
@@ -1174,8 +1214,7 @@ static int verify_auto_occupancy(uint64_t nm) { return nm == 8 ? 1 : auto_occupa
 xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                       size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream) {
   const KernelEventsScope events_scope;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   // every argument is checked before any work is queued on the stream
   if (reinterpret_cast<uintptr_t>(d_count) % 4 != 0) return XEC_INVALID_ALIGNMENT;
@@ -1226,60 +1265,46 @@ static xec_status update_impl(void* d_data, void* d_parity, const void* d_new, s
                               size_t n, void* d_scratch, size_t scratch_bytes,
                               hipStream_t stream) {
   g_update_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (n == 0 || S == 0) return XEC_SUCCESS;
   if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
   st = update_check_new(d_data, d_parity, d_new, n * bs, S, bs, k, m);
   if (st != XEC_SUCCESS) return st;
-  if (h_items == nullptr) return XEC_INVALID_COUNTS;
-  for (size_t t = 0; t < n; ++t) {  // strictly ascending = batch order, no duplicates
-    const uint32_t it = h_items[t];
-    if ((it & 0xFFu) >= k || (it >> 8) >= S || (t > 0 && it <= h_items[t - 1]))
-      return XEC_INVALID_COUNTS;
-  }
+  if (h_items == nullptr || !items_ascending(h_items, n, S, k)) return XEC_INVALID_COUNTS;
   const bool in_args = n <= xec::kArgItems;
   if (!in_args) {
-    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
-    if (d_scratch == nullptr || scratch_bytes < xec_update_scratch_bytes(n))
-      return XEC_INVALID_SIZE;
+    st = check_scratch(d_scratch, scratch_bytes, xec_update_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
   }
   if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
   const xec::LaunchShape ls = launch_shape(bs, 0);
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
   if (in_args) {
     g_update_tiling_used = XEC_TILING_ARG_LIST;
-    const hipError_t le = xec::launch_update(d_data, d_parity, d_new, nullptr, g, ls,
-                                             xec::kUpdateArgListTiles, stream, n, h_items);
-    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+    return launch_status(__LINE__,
+                         xec::launch_update(d_data, d_parity, d_new, nullptr, g, ls,
+                                            xec::kUpdateArgListTiles, stream, n, h_items));
   }
-  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
-  if (!sd.ok()) return DEVERR(hipSuccess);
-  bool fault = false;
-  Staging* sg = stage_acquire(n * 4, sd.device(), &fault);
-  if (sg == nullptr) return DEVERR(hipSuccess);
-  std::memcpy(sg->host, h_items, n * 4);
-  g_update_tiling_used = XEC_TILING_LIST;
-  hipError_t le = hipMemcpyAsync(d_scratch, sg->host, n * 4, hipMemcpyHostToDevice, stream);
-  const bool queued = le == hipSuccess;
-  if (queued)
-    le = xec::launch_update(d_data, d_parity, d_new, d_scratch, g, ls, xec::kUpdateListTiles,
-                            stream, n);
-  stage_release(sg, queued, stream, false);
-  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  return upload_list_and_launch(
+      n * 4, d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        std::memcpy(staged, h_items, n * 4);
+        g_update_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_update(d_data, d_parity, d_new, d_scratch, g, ls,
+                                  xec::kUpdateListTiles, stream, n);
+      });
 }
 
 xec_status xec_update(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
                       size_t k, size_t m, const uint32_t* h_items, size_t n_items,
                       void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
+  return guarded([&] {
     return update_impl(d_data, d_parity, d_new, S, bs, k, m, h_items, n_items, d_scratch,
                        scratch_bytes, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  });
 }
 
 size_t xec_update_scratch_bytes(size_t n_items) { return 4 * n_items; }
@@ -1291,8 +1316,7 @@ xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, si
                              hipStream_t stream) {
   const KernelEventsScope events_scope;
   g_update_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   // every argument is checked before any work is queued on the stream
@@ -1465,8 +1489,7 @@ static xec_status read_impl(const void* d_data, const void* d_parity, size_t S, 
                             size_t offset, size_t len, void* d_out, void* d_scratch,
                             size_t scratch_bytes, hipStream_t stream) {
   g_read_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (n == 0 || S == 0) return XEC_SUCCESS;
   st = read_check_range(d_data, d_parity, S, bs, k, m, h_items, n, offset, len, d_out);
@@ -1477,52 +1500,41 @@ static xec_status read_impl(const void* d_data, const void* d_parity, size_t S, 
   st = xec_scan_read_items(h_bitmap, S, k, m, h_items, n, in_args ? short_bits : nullptr, &n_lost);
   if (st != XEC_SUCCESS) return st;
   if (!in_args) {
-    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
-    if (d_scratch == nullptr || scratch_bytes < xec_read_scratch_bytes(n)) return XEC_INVALID_SIZE;
+    st = check_scratch(d_scratch, scratch_bytes, xec_read_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
   }
   if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
   const xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, n_lost));
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
   if (in_args) {
     g_read_tiling_used = XEC_TILING_ARG_LIST;
-    const hipError_t le =
-        xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadArgListTiles, offset, len, n,
-                         nullptr, nullptr, h_items, short_bits, stream);
-    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+    return launch_status(
+        __LINE__, xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadArgListTiles, offset,
+                                   len, n, nullptr, nullptr, h_items, short_bits, stream));
   }
-  // items, then their loss bits, staged in pinned memory and uploaded on
-  // `stream` itself in one copy, as xec_update uploads its list
-  const StreamDevice sd(stream);
-  if (!sd.ok()) return DEVERR(hipSuccess);
-  bool fault = false;
-  const size_t bytes = xec_read_scratch_bytes(n);
-  Staging* sg = stage_acquire(bytes, sd.device(), &fault);
-  if (sg == nullptr) return DEVERR(hipSuccess);
-  uint32_t* staged = static_cast<uint32_t*>(sg->host);
-  std::memcpy(staged, h_items, n * 4);
-  (void)xec_scan_read_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr);
-  g_read_tiling_used = XEC_TILING_LIST;
-  hipError_t le = hipMemcpyAsync(d_scratch, staged, bytes, hipMemcpyHostToDevice, stream);
-  const bool queued = le == hipSuccess;
-  if (queued)
-    le = xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadListTiles, offset, len, n,
-                          static_cast<const uint32_t*>(d_scratch), nullptr, nullptr, nullptr,
-                          stream);
-  stage_release(sg, queued, stream, false);
-  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  // items, then their loss bits, in one copy
+  return upload_list_and_launch(
+      xec_read_scratch_bytes(n), d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        std::memcpy(staged, h_items, n * 4);
+        (void)xec_scan_read_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr);
+        g_read_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_read(d_data, d_parity, d_out, g, ls, xec::kReadListTiles, offset, len,
+                                n, static_cast<const uint32_t*>(d_scratch), nullptr, nullptr,
+                                nullptr, stream);
+      });
 }
 
 xec_status xec_read(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                     size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n_items,
                     size_t offset, size_t len, void* d_out, void* d_scratch, size_t scratch_bytes,
                     hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
+  return guarded([&] {
     return read_impl(d_data, d_parity, S, bs, k, m, h_bitmap, h_items, n_items, offset, len, d_out,
                      d_scratch, scratch_bytes, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  });
 }
 
 size_t xec_read_scratch_bytes(size_t n_items) { return 4 * xec::read_list_words(n_items); }
@@ -1535,8 +1547,7 @@ xec_status xec_read_device(const void* d_data, const void* d_parity, size_t S, s
                            int32_t* d_status, hipStream_t stream) {
   const KernelEventsScope events_scope;
   g_read_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   // every argument is checked before any work is queued on the stream
   if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
@@ -1610,8 +1621,7 @@ static xec_status update_range_impl(void* d_data, void* d_parity, const void* d_
                                     size_t n, size_t offset, size_t len, uint64_t* d_digests,
                                     void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
   g_update_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (n == 0 || S == 0) return XEC_SUCCESS;
   if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
@@ -1619,54 +1629,41 @@ static xec_status update_range_impl(void* d_data, void* d_parity, const void* d_
   st = update_range_check(d_data, d_parity, d_new, n * len, h_items, S, bs, k, m, offset, len,
                           d_digests);
   if (st != XEC_SUCCESS) return st;
-  for (size_t t = 0; t < n; ++t) {  // strictly ascending = batch order, no duplicates
-    const uint32_t it = h_items[t];
-    if ((it & 0xFFu) >= k || (it >> 8) >= S || (t > 0 && it <= h_items[t - 1]))
-      return XEC_INVALID_COUNTS;
-  }
+  if (!items_ascending(h_items, n, S, k)) return XEC_INVALID_COUNTS;
   const bool in_args = n <= xec::kArgItems;
   if (!in_args) {
-    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
-    if (d_scratch == nullptr || scratch_bytes < xec_update_scratch_bytes(n))
-      return XEC_INVALID_SIZE;
+    st = check_scratch(d_scratch, scratch_bytes, xec_update_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
   }
   if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
   const xec::LaunchShape ls = launch_shape(bs, 0);
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
   if (in_args) {
     g_update_tiling_used = XEC_TILING_ARG_LIST;
-    const hipError_t le =
-        xec::launch_update_range(d_data, d_parity, d_new, nullptr, d_digests, g, ls,
-                                 xec::kUpdateArgListTiles, offset, len, stream, n, h_items);
-    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+    return launch_status(__LINE__, xec::launch_update_range(
+                                       d_data, d_parity, d_new, nullptr, d_digests, g, ls,
+                                       xec::kUpdateArgListTiles, offset, len, stream, n, h_items));
   }
-  const StreamDevice sd(stream);  // the stream's device, as in xec_decode
-  if (!sd.ok()) return DEVERR(hipSuccess);
-  bool fault = false;
-  Staging* sg = stage_acquire(n * 4, sd.device(), &fault);
-  if (sg == nullptr) return DEVERR(hipSuccess);
-  std::memcpy(sg->host, h_items, n * 4);
-  g_update_tiling_used = XEC_TILING_LIST;
-  hipError_t le = hipMemcpyAsync(d_scratch, sg->host, n * 4, hipMemcpyHostToDevice, stream);
-  const bool queued = le == hipSuccess;
-  if (queued)
-    le = xec::launch_update_range(d_data, d_parity, d_new, d_scratch, d_digests, g, ls,
-                                  xec::kUpdateListTiles, offset, len, stream, n);
-  stage_release(sg, queued, stream, false);
-  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  return upload_list_and_launch(
+      n * 4, d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        std::memcpy(staged, h_items, n * 4);
+        g_update_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_update_range(d_data, d_parity, d_new, d_scratch, d_digests, g, ls,
+                                        xec::kUpdateListTiles, offset, len, stream, n);
+      });
 }
 
 xec_status xec_update_range(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
                             size_t k, size_t m, const uint32_t* h_items, size_t n_items,
                             size_t offset, size_t len, uint64_t* d_digests, void* d_scratch,
                             size_t scratch_bytes, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
+  return guarded([&] {
     return update_range_impl(d_data, d_parity, d_new, S, bs, k, m, h_items, n_items, offset, len,
                              d_digests, d_scratch, scratch_bytes, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  });
 }
 
 xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_new, size_t S,
@@ -1675,8 +1672,7 @@ xec_status xec_update_range_device(void* d_data, void* d_parity, const void* d_n
                                    hipStream_t stream) {
   const KernelEventsScope events_scope;
   g_update_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   // every argument is checked before any work is queued on the stream
@@ -1705,8 +1701,7 @@ static xec_status write_impl(void* d_data, void* d_parity, const void* d_new, si
                              size_t n, size_t offset, size_t len, uint64_t* d_digests,
                              void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
   g_write_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (n == 0 || S == 0) return XEC_SUCCESS;
   if (k > kWorkItemMaxK || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
@@ -1720,52 +1715,41 @@ static xec_status write_impl(void* d_data, void* d_parity, const void* d_new, si
                             nullptr);
   if (st != XEC_SUCCESS) return st;
   if (!in_args) {
-    if (reinterpret_cast<uintptr_t>(d_scratch) % 4 != 0) return XEC_INVALID_ALIGNMENT;
-    if (d_scratch == nullptr || scratch_bytes < xec_write_scratch_bytes(n))
-      return XEC_INVALID_SIZE;
+    st = check_scratch(d_scratch, scratch_bytes, xec_write_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
   }
   if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
   const xec::LaunchShape ls = launch_shape(bs, 0);
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
   if (in_args) {
     g_write_tiling_used = XEC_TILING_ARG_LIST;
-    const hipError_t le =
-        xec::launch_write(d_data, d_parity, d_new, nullptr, nullptr, d_digests, g, ls,
-                          xec::kUpdateArgListTiles, offset, len, stream, n, h_items, short_bits);
-    return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+    return launch_status(
+        __LINE__, xec::launch_write(d_data, d_parity, d_new, nullptr, nullptr, d_digests, g, ls,
+                                    xec::kUpdateArgListTiles, offset, len, stream, n, h_items,
+                                    short_bits));
   }
-  // items, then their loss bits, staged in pinned memory and uploaded on
-  // `stream` itself in one copy, as xec_read uploads its list
-  const StreamDevice sd(stream);
-  if (!sd.ok()) return DEVERR(hipSuccess);
-  bool fault = false;
-  const size_t bytes = xec_write_scratch_bytes(n);
-  Staging* sg = stage_acquire(bytes, sd.device(), &fault);
-  if (sg == nullptr) return DEVERR(hipSuccess);
-  uint32_t* staged = static_cast<uint32_t*>(sg->host);
-  std::memcpy(staged, h_items, n * 4);
-  (void)xec_scan_write_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr, nullptr);
-  g_write_tiling_used = XEC_TILING_LIST;
-  hipError_t le = hipMemcpyAsync(d_scratch, staged, bytes, hipMemcpyHostToDevice, stream);
-  const bool queued = le == hipSuccess;
-  if (queued)
-    le = xec::launch_write(d_data, d_parity, d_new, d_scratch, nullptr, d_digests, g, ls,
-                           xec::kUpdateListTiles, offset, len, stream, n);
-  stage_release(sg, queued, stream, false);
-  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+  // items, then their loss bits, in one copy
+  return upload_list_and_launch(
+      xec_write_scratch_bytes(n), d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        std::memcpy(staged, h_items, n * 4);
+        (void)xec_scan_write_items(h_bitmap, S, k, m, h_items, n, staged + n, nullptr, nullptr);
+        g_write_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_write(d_data, d_parity, d_new, d_scratch, nullptr, d_digests, g, ls,
+                                 xec::kUpdateListTiles, offset, len, stream, n);
+      });
 }
 
 xec_status xec_write(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs, size_t k,
                      size_t m, const uint8_t* h_bitmap, const uint32_t* h_items, size_t n_items,
                      size_t offset, size_t len, uint64_t* d_digests, void* d_scratch,
                      size_t scratch_bytes, hipStream_t stream) {
-  const KernelEventsScope events_scope;
-  try {  // as xec_decode
+  return guarded([&] {
     return write_impl(d_data, d_parity, d_new, S, bs, k, m, h_bitmap, h_items, n_items, offset,
                       len, d_digests, d_scratch, scratch_bytes, stream);
-  } catch (...) {
-    return XEC_DEVICE_ERROR;
-  }
+  });
 }
 
 size_t xec_write_scratch_bytes(size_t n_items) { return 4 * xec::write_list_words(n_items); }
@@ -1778,8 +1762,7 @@ xec_status xec_write_device(void* d_data, void* d_parity, const void* d_new, siz
                             hipStream_t stream) {
   const KernelEventsScope events_scope;
   g_write_tiling_used = 0;
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   // every argument is checked before any work is queued on the stream
@@ -1803,8 +1786,7 @@ xec_status xec_write_device(void* d_data, void* d_parity, const void* d_new, siz
 
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
-  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
-  xec_status st = xec_check_args(d_data, d_parity, bs, k, m);
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (S == 0) return XEC_SUCCESS;
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, xec::LaunchShape{256, 1, 0, false, 0});

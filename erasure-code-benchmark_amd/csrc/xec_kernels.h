@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "xec_dispatch.h"
+
 namespace xec {
 
 // Batch geometry.  A tile is one class of one stripe over threads*unroll
@@ -154,16 +156,16 @@ constexpr int kDecodeArgMaskStripeTiles = 6;
 constexpr uint64_t kArgMaskMaxK = 32;
 // The list travels in the kernel arguments, so a launch ships the whole array
 // whatever the list's length: each kernel that takes one is compiled for three
-// capacities and the launch picks the smallest that holds the list (VERDICT
-// r05 item 4).  A kernel with 4 KiB of arguments costs 0.15-0.4 us more per
-// synchronous call than the same kernel with 256 B (tools/latency,
-// profiles/r06b): small, but free to avoid.
+// capacities and the launch picks the smallest that holds the list
+// (arg_items_capacity and with_capacity, xec_dispatch.h).
+// A kernel with 4 KiB of arguments costs 0.15-0.4 us more per synchronous call
+// than the same kernel with 256 B (tools/latency, profiles/r06b): small, but
+// free to avoid.
 constexpr uint64_t kArgItems = 1024;  // the largest capacity
 template <uint32_t N>
 struct ArgItems {
   uint32_t v[N];
 };
-inline uint32_t arg_items_capacity(uint64_t n) { return n <= 64 ? 64 : n <= 256 ? 256 : 1024; }
 hipError_t launch_decode(void* d_data, const void* d_parity, const uint8_t* d_bitmap,
                          const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
                          uint64_t n_items = 0, const uint32_t* h_items = nullptr);

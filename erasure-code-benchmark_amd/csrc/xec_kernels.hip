@@ -855,13 +855,6 @@ __global__ __launch_bounds__(256) void fill_kernel(uint64_t* buf, uint64_t S, ui
 // ---------------------------------------------------------------------------
 namespace {
 
-template <int NM, int U, bool NT, int T>
-hipError_t launch_encode_t(const void* d, void* p, const Geometry& g, uint32_t grid,
-                           uint32_t lds, hipStream_t s) {
-  return launch_codec(encode_kernel<NM, U, NT, T>, grid, T, lds, s,
-                      static_cast<const uint8_t*>(d), static_cast<uint8_t*>(p), g);
-}
-
 // The first n of h_items in an ArgItems<CAP>, the rest zero (the kernel never
 // reads past n; zeroed so a launch's arguments depend on the list alone).
 template <uint32_t CAP>
@@ -872,106 +865,34 @@ ArgItems<CAP> arg_items(const uint32_t* h_items, uint64_t n) {
   return a;
 }
 
-struct ArgList {
-  const uint32_t* items;  // host memory, read at launch
-  uint64_t n;             // <= kArgItems
-};
-
-template <int NM, int U, bool NT, int T>
-hipError_t launch_decode_t(void* d, const void* p, const uint8_t* bm, const Geometry& g,
-                           int tiling, uint32_t grid, uint32_t lds, hipStream_t s,
-                           const ArgList& al) {
-  uint8_t* dd = static_cast<uint8_t*>(d);
-  const uint8_t* pp = static_cast<const uint8_t*>(p);
-  const uint32_t* list = reinterpret_cast<const uint32_t*>(bm);
-  if (tiling == kDecodeDevListTiles)
-    return launch_codec(decode_devlist_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, list, g);
-  if (tiling == kDecodeArgListTiles) {
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(decode_arglist_kernel<NM, U, NT, T, 64>, grid, T, lds, s, dd, pp, g,
-                      arg_items<64>(al.items, al.n));
-      case 256:
-        return launch_codec(decode_arglist_kernel<NM, U, NT, T, 256>, grid, T, lds, s, dd, pp, g,
-                      arg_items<256>(al.items, al.n));
-      default:
-        return launch_codec(decode_arglist_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, dd, pp, g,
-                      arg_items<1024>(al.items, al.n));
-    }
-  }
-  if (tiling == kDecodeArgMaskTiles || tiling == kDecodeArgMaskStripeTiles) {
-    const uint32_t by_class = tiling == kDecodeArgMaskTiles;
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(decode_argmask_kernel<NM, U, NT, T, 64>, grid, T, lds, s, dd, pp, g,
-                            by_class, arg_items<64>(al.items, al.n));
-      case 256:
-        return launch_codec(decode_argmask_kernel<NM, U, NT, T, 256>, grid, T, lds, s, dd, pp, g,
-                            by_class, arg_items<256>(al.items, al.n));
-      default:
-        return launch_codec(decode_argmask_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, dd, pp, g,
-                            by_class, arg_items<1024>(al.items, al.n));
-    }
-  }
-  if (tiling == kDecodeListTiles)
-    return launch_codec(decode_list_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, list, g);
-  if (tiling == kDecodeClassTiles)
-    return launch_codec(decode_class_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, bm, g);
-  return launch_codec(decode_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, bm, g);
-}
-
-// Member counts (k/m) compiled fully unrolled: those of the reference's sweep
-// (bm_config.cpp:7-11) and BASELINE.json -- 1, 2, 4, 8, 16, 32; others run the
-// generic loop (NM = 0).
-#define XEC_NM_SWITCH(NMV, CALL)                  \
-  switch (NMV) {                                  \
-    case 1: { constexpr int NM = 1; CALL; }       \
-    case 2: { constexpr int NM = 2; CALL; }       \
-    case 4: { constexpr int NM = 4; CALL; }       \
-    case 8: { constexpr int NM = 8; CALL; }       \
-    case 16: { constexpr int NM = 16; CALL; }     \
-    case 32: { constexpr int NM = 32; CALL; }     \
-    default: { constexpr int NM = 0; CALL; }      \
-  }
-
-template <int U, bool NT, int T>
-hipError_t enc_nm(const void* d, void* p, const Geometry& g, uint32_t grid, uint32_t lds,
-                  hipStream_t s) {
-  XEC_NM_SWITCH(g.nm, return (launch_encode_t<NM, U, NT, T>(d, p, g, grid, lds, s)))
-}
-
-template <int U, bool NT, int T>
-hipError_t dec_nm(void* d, const void* p, const uint8_t* bm, const Geometry& g, int tiling,
-                  uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
-  XEC_NM_SWITCH(g.nm,
-                return (launch_decode_t<NM, U, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)))
-}
-
-template <bool NT, int T>
-hipError_t enc_u(const void* d, void* p, const Geometry& g, int unroll, uint32_t grid,
-                 uint32_t lds, hipStream_t s) {
-  return unroll == 2 ? enc_nm<2, NT, T>(d, p, g, grid, lds, s)
-                     : enc_nm<1, NT, T>(d, p, g, grid, lds, s);
-}
-
-template <bool NT, int T>
-hipError_t dec_u(void* d, const void* p, const uint8_t* bm, const Geometry& g, int tiling,
-                 int unroll, uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
-  return unroll == 2 ? dec_nm<2, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)
-                     : dec_nm<1, NT, T>(d, p, bm, g, tiling, grid, lds, s, a);
+// g_class over bytes [offset, offset + len) of each block (read, ranged
+// update, degraded write): the tiles are chunks of the RANGE, `units` items or
+// classes of them, and there is no column rotation.
+Geometry range_geometry(const Geometry& g_class, const LaunchShape& ls, uint64_t len,
+                        uint64_t units) {
+  Geometry g = g_class;
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;
+  g.total_tiles = units * g.tiles_per_block;
+  g.rot = 0;
+  return g;
 }
 
 }  // namespace
 
+// Every launch_X below: its preconditions, then one with_shape (xec_dispatch.h)
+// whose lambda picks the kernel by tiling and, where a list travels in the
+// kernel arguments, its capacity by with_capacity.
+
 hipError_t launch_encode(const void* d_data, void* d_parity, const Geometry& g,
                          const LaunchShape& ls, hipStream_t s) {
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
-  const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? enc_u<true, 256>(d_data, d_parity, g, ls.unroll, grid, lds, s)
-                 : enc_u<false, 256>(d_data, d_parity, g, ls.unroll, grid, lds, s);
-  return ls.nt ? enc_u<true, 64>(d_data, d_parity, g, ls.unroll, grid, lds, s)
-               : enc_u<false, 64>(d_data, d_parity, g, ls.unroll, grid, lds, s);
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    return launch_codec(encode_kernel<NM, U, NT, T>, grid, T, ls.lds_bytes, s,
+                        static_cast<const uint8_t*>(d_data), static_cast<uint8_t*>(d_parity), g);
+  });
 }
 
 hipError_t launch_decode(void* d_data, const void* d_parity, const uint8_t* d_bitmap,
@@ -999,17 +920,40 @@ hipError_t launch_decode(void* d_data, const void* d_parity, const uint8_t* d_bi
   if ((tiling == kDecodeArgMaskTiles || tiling == kDecodeArgMaskStripeTiles) &&
       (n_items != g.S || n_items > kArgItems || g.k > kArgMaskMaxK || h_items == nullptr))
     return hipErrorInvalidValue;
-  const ArgList a{h_items, n_items};
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt
-               ? dec_u<true, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
-               : dec_u<false, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
-                                   a);
-  return ls.nt ? dec_u<true, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
-               : dec_u<false, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
-                                  a);
+  uint8_t* dd = static_cast<uint8_t*>(d_data);
+  const uint8_t* pp = static_cast<const uint8_t*>(d_parity);
+  const uint32_t* list = reinterpret_cast<const uint32_t*>(d_bitmap);
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    switch (tiling) {
+      case kDecodeDevListTiles:
+        return launch_codec(decode_devlist_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, list, g);
+      case kDecodeArgListTiles:
+        return with_capacity(n_items, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;
+          return launch_codec(decode_arglist_kernel<NM, U, NT, T, CAP>, grid, T, lds, s, dd, pp, g,
+                              arg_items<CAP>(h_items, n_items));
+        });
+      case kDecodeArgMaskTiles:
+      case kDecodeArgMaskStripeTiles:
+        return with_capacity(n_items, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;
+          const uint32_t by_class = tiling == kDecodeArgMaskTiles;
+          return launch_codec(decode_argmask_kernel<NM, U, NT, T, CAP>, grid, T, lds, s, dd, pp, g,
+                              by_class, arg_items<CAP>(h_items, n_items));
+        });
+      case kDecodeListTiles:
+        return launch_codec(decode_list_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, list, g);
+      case kDecodeClassTiles:
+        return launch_codec(decode_class_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, d_bitmap,
+                            g);
+      default:
+        return launch_codec(decode_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, d_bitmap, g);
+    }
+  });
 }
 
 hipError_t launch_check(const uint8_t* d_bitmap, const Geometry& g, int32_t* d_status,
@@ -1042,17 +986,11 @@ hipError_t launch_gather(const void* d_data, void* d_out, uint64_t k, uint64_t b
   const uint8_t* src = static_cast<const uint8_t*>(d_data);
   uint8_t* dst = static_cast<uint8_t*>(d_out);
   const uint32_t grid = grid_for(n, 0, 256);
-  switch (arg_items_capacity(n)) {
-    case 64:
-      return launch(gather_kernel<64>, grid, 256, 0, s, src, dst, k, bs, (uint32_t)n,
-                    arg_items<64>(h_items, n));
-    case 256:
-      return launch(gather_kernel<256>, grid, 256, 0, s, src, dst, k, bs, (uint32_t)n,
-                    arg_items<256>(h_items, n));
-    default:
-      return launch(gather_kernel<1024>, grid, 256, 0, s, src, dst, k, bs, (uint32_t)n,
-                    arg_items<1024>(h_items, n));
-  }
+  return with_capacity(n, [&](auto cap) {
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch(gather_kernel<CAP>, grid, 256, 0, s, src, dst, k, bs, (uint32_t)n,
+                  arg_items<CAP>(h_items, n));
+  });
 }
 
 hipError_t launch_fill(void* d_buf, uint64_t S, uint64_t words, uint64_t seed_base,
@@ -1065,70 +1003,7 @@ hipError_t launch_fill(void* d_buf, uint64_t S, uint64_t words, uint64_t seed_ba
                 static_cast<uint64_t*>(d_buf), S, words, seed_base);
 }
 
-// ---- repair and verify launchers (after every older launcher, so the older
-// kernels keep their place in the code object) ----------------------------
-namespace {
-
-template <int NM, int U, bool NT, int T>
-hipError_t launch_repair_t(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling,
-                           uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& al) {
-  uint8_t* dd = static_cast<uint8_t*>(d);
-  uint8_t* pp = static_cast<uint8_t*>(p);
-  if (tiling == kRepairArgListTiles) {
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 64>, grid, T, lds, s, dd, pp, g,
-                            arg_items<64>(al.items, al.n));
-      case 256:
-        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 256>, grid, T, lds, s, dd, pp, g,
-                            arg_items<256>(al.items, al.n));
-      default:
-        return launch_codec(repair_arglist_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, dd, pp, g,
-                            arg_items<1024>(al.items, al.n));
-    }
-  }
-  if (tiling == kRepairListTiles)
-    return launch_codec(repair_list_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp,
-                        reinterpret_cast<const uint32_t*>(bm), g);
-  return launch_codec(repair_class_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, bm, g);
-}
-
-template <int NM, int U, bool NT, int T>
-hipError_t launch_verify_t(const void* d, const void* p, uint8_t* flags, const Geometry& g,
-                           uint32_t grid, uint32_t lds, hipStream_t s) {
-  return launch_codec(verify_kernel<NM, U, NT, T>, grid, T, lds, s,
-                      static_cast<const uint8_t*>(d), static_cast<const uint8_t*>(p), flags, g);
-}
-
-template <int U, bool NT, int T>
-hipError_t rep_nm(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling,
-                  uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
-  XEC_NM_SWITCH(g.nm,
-                return (launch_repair_t<NM, U, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)))
-}
-
-template <int U, bool NT, int T>
-hipError_t ver_nm(const void* d, const void* p, uint8_t* flags, const Geometry& g, uint32_t grid,
-                  uint32_t lds, hipStream_t s) {
-  XEC_NM_SWITCH(g.nm, return (launch_verify_t<NM, U, NT, T>(d, p, flags, g, grid, lds, s)))
-}
-
-template <bool NT, int T>
-hipError_t rep_u(void* d, void* p, const uint8_t* bm, const Geometry& g, int tiling, int unroll,
-                 uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& a) {
-  return unroll == 2 ? rep_nm<2, NT, T>(d, p, bm, g, tiling, grid, lds, s, a)
-                     : rep_nm<1, NT, T>(d, p, bm, g, tiling, grid, lds, s, a);
-}
-
-template <bool NT, int T>
-hipError_t ver_u(const void* d, const void* p, uint8_t* flags, const Geometry& g, int unroll,
-                 uint32_t grid, uint32_t lds, hipStream_t s) {
-  return unroll == 2 ? ver_nm<2, NT, T>(d, p, flags, g, grid, lds, s)
-                     : ver_nm<1, NT, T>(d, p, flags, g, grid, lds, s);
-}
-
-}  // namespace
-
+// ---- repair and verify launchers ----------------------------------------
 hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
                          const Geometry& g_class, const LaunchShape& ls, int tiling,
                          hipStream_t s, uint64_t n_items, const uint32_t* h_items) {
@@ -1142,29 +1017,41 @@ hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
   if (g.k + g.m > 256 && tiling != kRepairClassTiles) return hipErrorInvalidValue;
   if (tiling == kRepairArgListTiles && (n_items > kArgItems || h_items == nullptr))
     return hipErrorInvalidValue;
-  const ArgList a{h_items, n_items};
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt
-               ? rep_u<true, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
-               : rep_u<false, 256>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
-                                   a);
-  return ls.nt ? rep_u<true, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s, a)
-               : rep_u<false, 64>(d_data, d_parity, d_bitmap, g, tiling, ls.unroll, grid, lds, s,
-                                  a);
+  uint8_t* dd = static_cast<uint8_t*>(d_data);
+  uint8_t* pp = static_cast<uint8_t*>(d_parity);
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    switch (tiling) {
+      case kRepairArgListTiles:
+        return with_capacity(n_items, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;
+          return launch_codec(repair_arglist_kernel<NM, U, NT, T, CAP>, grid, T, lds, s, dd, pp, g,
+                              arg_items<CAP>(h_items, n_items));
+        });
+      case kRepairListTiles:
+        return launch_codec(repair_list_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp,
+                            reinterpret_cast<const uint32_t*>(d_bitmap), g);
+      default:
+        return launch_codec(repair_class_kernel<NM, U, NT, T>, grid, T, lds, s, dd, pp, d_bitmap,
+                            g);
+    }
+  });
 }
 
 hipError_t launch_verify(const void* d_data, const void* d_parity, uint8_t* d_flags,
                          const Geometry& g, const LaunchShape& ls, hipStream_t s) {
   if (g.total_tiles == 0) return hipSuccess;
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
-  const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? ver_u<true, 256>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s)
-                 : ver_u<false, 256>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s);
-  return ls.nt ? ver_u<true, 64>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s)
-               : ver_u<false, 64>(d_data, d_parity, d_flags, g, ls.unroll, grid, lds, s);
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    return launch_codec(verify_kernel<NM, U, NT, T>, grid, T, ls.lds_bytes, s,
+                        static_cast<const uint8_t*>(d_data),
+                        static_cast<const uint8_t*>(d_parity), d_flags, g);
+  });
 }
 
 hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_count,
@@ -1174,46 +1061,7 @@ hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_co
   return launch(count_flags_kernel<256>, grid, 256, 0, s, d_flags, n, d_count);
 }
 
-// ---- update launchers (after every older launcher, as above) -----------------
-namespace {
-
-template <int U, bool NT, int T>
-hipError_t launch_update_t(void* d, void* p, const void* fresh, const void* sel,
-                           const Geometry& g, int tiling, uint32_t grid, uint32_t lds,
-                           hipStream_t s, const ArgList& al) {
-  uint8_t* dd = static_cast<uint8_t*>(d);
-  uint8_t* pp = static_cast<uint8_t*>(p);
-  const uint8_t* ff = static_cast<const uint8_t*>(fresh);
-  if (tiling == kUpdateArgListTiles) {
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(update_arglist_kernel<U, NT, T, 64>, grid, T, lds, s, dd, pp, ff, g,
-                            arg_items<64>(al.items, al.n));
-      case 256:
-        return launch_codec(update_arglist_kernel<U, NT, T, 256>, grid, T, lds, s, dd, pp, ff, g,
-                            arg_items<256>(al.items, al.n));
-      default:
-        return launch_codec(update_arglist_kernel<U, NT, T, 1024>, grid, T, lds, s, dd, pp, ff, g,
-                            arg_items<1024>(al.items, al.n));
-    }
-  }
-  if (tiling == kUpdateListTiles)
-    return launch_codec(update_list_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
-                        static_cast<const uint32_t*>(sel), g);
-  return launch_codec(update_class_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
-                      static_cast<const uint8_t*>(sel), g);
-}
-
-template <bool NT, int T>
-hipError_t upd_u(void* d, void* p, const void* fresh, const void* sel, const Geometry& g,
-                 int tiling, int unroll, uint32_t grid, uint32_t lds, hipStream_t s,
-                 const ArgList& a) {
-  return unroll == 2 ? launch_update_t<2, NT, T>(d, p, fresh, sel, g, tiling, grid, lds, s, a)
-                     : launch_update_t<1, NT, T>(d, p, fresh, sel, g, tiling, grid, lds, s, a);
-}
-
-}  // namespace
-
+// ---- update launcher -------------------------------------------------------
 hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
                          const Geometry& g_class, const LaunchShape& ls, int tiling,
                          hipStream_t s, uint64_t n_items, const uint32_t* h_items) {
@@ -1229,23 +1077,33 @@ hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const 
   if (tiling == kUpdateArgListTiles && (n_items > kArgItems || h_items == nullptr))
     return hipErrorInvalidValue;
   if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
-  const ArgList a{h_items, n_items};
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? upd_u<true, 256>(d_data, d_parity, d_new, d_sel, g, tiling, ls.unroll, grid,
-                                    lds, s, a)
-                 : upd_u<false, 256>(d_data, d_parity, d_new, d_sel, g, tiling, ls.unroll, grid,
-                                     lds, s, a);
-  return ls.nt ? upd_u<true, 64>(d_data, d_parity, d_new, d_sel, g, tiling, ls.unroll, grid, lds,
-                                 s, a)
-               : upd_u<false, 64>(d_data, d_parity, d_new, d_sel, g, tiling, ls.unroll, grid, lds,
-                                  s, a);
+  uint8_t* dd = static_cast<uint8_t*>(d_data);
+  uint8_t* pp = static_cast<uint8_t*>(d_parity);
+  const uint8_t* ff = static_cast<const uint8_t*>(d_new);
+  return with_shape(ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    switch (tiling) {
+      case kUpdateArgListTiles:
+        return with_capacity(n_items, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;
+          return launch_codec(update_arglist_kernel<U, NT, T, CAP>, grid, T, lds, s, dd, pp, ff, g,
+                              arg_items<CAP>(h_items, n_items));
+        });
+      case kUpdateListTiles:
+        return launch_codec(update_list_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
+                            static_cast<const uint32_t*>(d_sel), g);
+      default:
+        return launch_codec(update_class_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
+                            static_cast<const uint8_t*>(d_sel), g);
+    }
+  });
 }
 
 // ---------------------------------------------------------------------------
-// digest and locate (xec_digest, xec_locate).  Kernels and launchers together,
-// after every older one, so the older kernels keep their place.
+// digest and locate (xec_digest, xec_locate).  Kernels and launchers together.
 //
 //   digest(block) = sum over its u64 words w[n] of splitmix_at(w[n], n)  (mod 2^64)
 //
@@ -1420,8 +1278,7 @@ hipError_t launch_locate_compare(const uint64_t* d_fresh, const uint64_t* d_stor
 }
 
 // ---------------------------------------------------------------------------
-// degraded read (xec_read, xec_read_device).  Kernels and launchers together,
-// after every older one, so the older kernels keep their place.
+// degraded read (xec_read, xec_read_device).  Kernels and launchers together.
 //
 // Item e = c << 8 | i (repair's packing) asks for bytes [offset, offset + len)
 // of block i of stripe c, delivered at out + e*len.  A tile is (item, chunk of
@@ -1666,56 +1523,6 @@ __global__ __launch_bounds__(256) void read_check_kernel(const uint8_t* __restri
   }
 }
 
-namespace {
-
-template <int NM, int U, bool NT, int T>
-hipError_t launch_read_t(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g,
-                         int tiling, const ReadRange& rr, const uint32_t* d_items,
-                         const uint8_t* bm, const ArgList& al, const uint32_t* h_lost,
-                         uint32_t grid, uint32_t lds, hipStream_t s) {
-  if (tiling == kReadArgListTiles) {
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(read_arglist_kernel<NM, U, NT, T, 64>, grid, T, lds, s, d, p, out, rr,
-                            g, arg_items<64>(al.items, al.n),
-                            arg_items<2>(h_lost, (al.n + 31) / 32));
-      case 256:
-        return launch_codec(read_arglist_kernel<NM, U, NT, T, 256>, grid, T, lds, s, d, p, out,
-                            rr, g, arg_items<256>(al.items, al.n),
-                            arg_items<8>(h_lost, (al.n + 31) / 32));
-      default:
-        return launch_codec(read_arglist_kernel<NM, U, NT, T, 1024>, grid, T, lds, s, d, p, out,
-                            rr, g, arg_items<1024>(al.items, al.n),
-                            arg_items<32>(h_lost, (al.n + 31) / 32));
-    }
-  }
-  if (tiling == kReadListTiles)
-    return launch_codec(read_list_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items, rr, g);
-  return launch_codec(read_dev_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items, bm, rr,
-                      g);
-}
-
-template <int U, bool NT, int T>
-hipError_t read_nm(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g, int tiling,
-                   const ReadRange& rr, const uint32_t* d_items, const uint8_t* bm,
-                   const ArgList& al, const uint32_t* h_lost, uint32_t grid, uint32_t lds,
-                   hipStream_t s) {
-  XEC_NM_SWITCH(g.nm, return (launch_read_t<NM, U, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al,
-                                                          h_lost, grid, lds, s)))
-}
-
-template <bool NT, int T>
-hipError_t read_u(const uint8_t* d, const uint8_t* p, uint8_t* out, const Geometry& g, int tiling,
-                  int unroll, const ReadRange& rr, const uint32_t* d_items, const uint8_t* bm,
-                  const ArgList& al, const uint32_t* h_lost, uint32_t grid, uint32_t lds,
-                  hipStream_t s) {
-  return unroll == 2
-             ? read_nm<2, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al, h_lost, grid, lds, s)
-             : read_nm<1, NT, T>(d, p, out, g, tiling, rr, d_items, bm, al, h_lost, grid, lds, s);
-}
-
-}  // namespace
-
 hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out,
                        const Geometry& g_class, const LaunchShape& ls, int tiling, uint64_t offset,
                        uint64_t len, uint64_t n_items, const uint32_t* d_items,
@@ -1730,27 +1537,32 @@ hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out,
                                   : d_items == nullptr)
     return hipErrorInvalidValue;
   if (tiling == kReadDevTiles && g_class.gate == nullptr) return hipErrorInvalidValue;
-  Geometry g = g_class;
-  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
-  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
-  g.total_tiles = n_items * g.tiles_per_block;
-  g.rot = 0;
+  const Geometry g = range_geometry(g_class, ls, len, n_items);
   const ReadRange rr{offset, len};
-  const ArgList a{h_items, n_items};
   const uint8_t* d = static_cast<const uint8_t*>(d_data);
   const uint8_t* p = static_cast<const uint8_t*>(d_parity);
   uint8_t* out = static_cast<uint8_t*>(d_out);
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? read_u<true, 256>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
-                                     h_lost, grid, lds, s)
-                 : read_u<false, 256>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
-                                      h_lost, grid, lds, s);
-  return ls.nt ? read_u<true, 64>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a, h_lost,
-                                  grid, lds, s)
-               : read_u<false, 64>(d, p, out, g, tiling, ls.unroll, rr, d_items, d_bitmap, a,
-                                   h_lost, grid, lds, s);
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    switch (tiling) {
+      case kReadArgListTiles:
+        return with_capacity(n_items, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;  // and one `lost` bit per item
+          return launch_codec(read_arglist_kernel<NM, U, NT, T, CAP>, grid, T, lds, s, d, p, out,
+                              rr, g, arg_items<CAP>(h_items, n_items),
+                              arg_items<CAP / 32>(h_lost, (n_items + 31) / 32));
+        });
+      case kReadListTiles:
+        return launch_codec(read_list_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items,
+                            rr, g);
+      default:
+        return launch_codec(read_dev_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_items,
+                            d_bitmap, rr, g);
+    }
+  });
 }
 
 hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
@@ -1762,8 +1574,7 @@ hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, u
 
 // ---------------------------------------------------------------------------
 // ranged update (xec_update_range, xec_update_range_device).  Kernels and
-// launchers together, after every older one, so the older kernels keep their
-// place.
+// launchers together.
 //
 // The update above over bytes [offset, offset + len) of each named block only,
 //   parity[c][i % m][range] ^= data[c][i][range] ^ new;   data[c][i][range] = new
@@ -1970,52 +1781,6 @@ __global__ __launch_bounds__(T) void patch_class_kernel(uint8_t* data, uint8_t* 
   }
 }
 
-namespace {
-
-template <int U, bool NT, int T, bool DIG>
-hipError_t launch_patch_t(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
-                          uint64_t* dig, const ReadRange& rr, const Geometry& g, int tiling,
-                          uint32_t grid, uint32_t lds, hipStream_t s, const ArgList& al) {
-  if (tiling == kUpdateArgListTiles) {
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 64>, grid, T, lds, s, d, p, fresh,
-                            dig, rr, g, arg_items<64>(al.items, al.n));
-      case 256:
-        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 256>, grid, T, lds, s, d, p, fresh,
-                            dig, rr, g, arg_items<256>(al.items, al.n));
-      default:
-        return launch_codec(patch_arglist_kernel<U, NT, T, DIG, 1024>, grid, T, lds, s, d, p,
-                            fresh, dig, rr, g, arg_items<1024>(al.items, al.n));
-    }
-  }
-  if (tiling == kUpdateListTiles)
-    return launch_codec(patch_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
-                        static_cast<const uint32_t*>(sel), dig, rr, g);
-  return launch_codec(patch_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
-                      static_cast<const uint8_t*>(sel), dig, rr, g);
-}
-
-template <bool NT, int T, bool DIG>
-hipError_t patch_u(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel, uint64_t* dig,
-                   const ReadRange& rr, const Geometry& g, int tiling, int unroll, uint32_t grid,
-                   uint32_t lds, hipStream_t s, const ArgList& a) {
-  return unroll == 2
-             ? launch_patch_t<2, NT, T, DIG>(d, p, fresh, sel, dig, rr, g, tiling, grid, lds, s, a)
-             : launch_patch_t<1, NT, T, DIG>(d, p, fresh, sel, dig, rr, g, tiling, grid, lds, s, a);
-}
-
-template <bool NT, int T>
-hipError_t patch_dig(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel, uint64_t* dig,
-                     const ReadRange& rr, const Geometry& g, int tiling, int unroll, uint32_t grid,
-                     uint32_t lds, hipStream_t s, const ArgList& a) {
-  return dig != nullptr
-             ? patch_u<NT, T, true>(d, p, fresh, sel, dig, rr, g, tiling, unroll, grid, lds, s, a)
-             : patch_u<NT, T, false>(d, p, fresh, sel, dig, rr, g, tiling, unroll, grid, lds, s, a);
-}
-
-}  // namespace
-
 hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
                                uint64_t* d_digests, const Geometry& g_class, const LaunchShape& ls,
                                int tiling, uint64_t offset, uint64_t len, hipStream_t s,
@@ -2023,39 +1788,47 @@ hipError_t launch_update_range(void* d_data, void* d_parity, const void* d_new, 
   if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs ||
       tiling < kUpdateClassTiles || tiling > kUpdateArgListTiles)
     return hipErrorInvalidValue;
-  Geometry g = g_class;
-  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
-  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
-  g.total_tiles = (tiling == kUpdateClassTiles ? g.S * g.m : n_items) * g.tiles_per_block;
-  g.rot = 0;
+  const Geometry g = range_geometry(
+      g_class, ls, len, tiling == kUpdateClassTiles ? g_class.S * g_class.m : n_items);
   if (g.total_tiles == 0) return hipSuccess;
   if (g.k > 256 && tiling != kUpdateClassTiles) return hipErrorInvalidValue;
   if (tiling == kUpdateArgListTiles && (n_items > kArgItems || h_items == nullptr))
     return hipErrorInvalidValue;
   if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
   const ReadRange rr{offset, len};
-  const ArgList a{h_items, n_items};
   uint8_t* d = static_cast<uint8_t*>(d_data);
   uint8_t* p = static_cast<uint8_t*>(d_parity);
   const uint8_t* f = static_cast<const uint8_t*>(d_new);
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? patch_dig<true, 256>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
-                                        lds, s, a)
-                 : patch_dig<false, 256>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
-                                         lds, s, a);
-  return ls.nt ? patch_dig<true, 64>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
-                                     lds, s, a)
-               : patch_dig<false, 64>(d, p, f, d_sel, d_digests, rr, g, tiling, ls.unroll, grid,
-                                      lds, s, a);
+  return with_shape(ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    return with_bool(d_digests != nullptr, [&](auto dig) {
+      constexpr bool DIG = decltype(dig)::value;
+      switch (tiling) {
+        case kUpdateArgListTiles:
+          return with_capacity(n_items, [&](auto cap) {
+            constexpr uint32_t CAP = decltype(cap)::value;
+            return launch_codec(patch_arglist_kernel<U, NT, T, DIG, CAP>, grid, T, lds, s, d, p, f,
+                                d_digests, rr, g, arg_items<CAP>(h_items, n_items));
+          });
+        case kUpdateListTiles:
+          return launch_codec(patch_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, f,
+                              static_cast<const uint32_t*>(d_sel), d_digests, rr, g);
+        default:
+          return launch_codec(patch_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, f,
+                              static_cast<const uint8_t*>(d_sel), d_digests, rr, g);
+      }
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
 // degraded write (xec_write, xec_write_device).  Kernels and launchers
-// together, after every older one, so the older kernels keep their place; they
-// stand beside patch_* and share only its lane helpers (patch_fold, patch_mix,
-// patch_wave_add), so the patch kernels stay what they were.
+// together; they stand beside patch_* and share only its lane helpers
+// (patch_fold, patch_mix, patch_wave_add), so the patch kernels stay what they
+// were.
 //
 // The ranged update above under a loss bitmap: a lost block is never read and
 // never written.  Tiles, range addressing, ownership (the first item of a
@@ -2453,60 +2226,6 @@ __global__ __launch_bounds__(256) void write_check_kernel(const uint8_t* __restr
   }
 }
 
-namespace {
-
-template <int U, bool NT, int T, bool DIG>
-hipError_t launch_write_t(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
-                          const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
-                          int tiling, uint32_t grid, uint32_t lds, hipStream_t s,
-                          const ArgList& al, const uint32_t* h_bits) {
-  if (tiling == kUpdateArgListTiles) {
-    const uint64_t words = (al.n + 15) / 16;
-    switch (arg_items_capacity(al.n)) {
-      case 64:
-        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 64>, grid, T, lds, s, d, p, fresh,
-                            dig, rr, g, arg_items<64>(al.items, al.n), arg_items<4>(h_bits, words));
-      case 256:
-        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 256>, grid, T, lds, s, d, p, fresh,
-                            dig, rr, g, arg_items<256>(al.items, al.n),
-                            arg_items<16>(h_bits, words));
-      default:
-        return launch_codec(write_arglist_kernel<U, NT, T, DIG, 1024>, grid, T, lds, s, d, p,
-                            fresh, dig, rr, g, arg_items<1024>(al.items, al.n),
-                            arg_items<64>(h_bits, words));
-    }
-  }
-  if (tiling == kUpdateListTiles)
-    return launch_codec(write_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
-                        static_cast<const uint32_t*>(sel), dig, rr, g);
-  return launch_codec(write_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, fresh,
-                      static_cast<const uint8_t*>(sel), bm, dig, rr, g);
-}
-
-template <bool NT, int T, bool DIG>
-hipError_t write_u(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
-                   const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
-                   int tiling, int unroll, uint32_t grid, uint32_t lds, hipStream_t s,
-                   const ArgList& a, const uint32_t* h_bits) {
-  return unroll == 2 ? launch_write_t<2, NT, T, DIG>(d, p, fresh, sel, bm, dig, rr, g, tiling, grid,
-                                                     lds, s, a, h_bits)
-                     : launch_write_t<1, NT, T, DIG>(d, p, fresh, sel, bm, dig, rr, g, tiling, grid,
-                                                     lds, s, a, h_bits);
-}
-
-template <bool NT, int T>
-hipError_t write_dig(uint8_t* d, uint8_t* p, const uint8_t* fresh, const void* sel,
-                     const uint8_t* bm, uint64_t* dig, const ReadRange& rr, const Geometry& g,
-                     int tiling, int unroll, uint32_t grid, uint32_t lds, hipStream_t s,
-                     const ArgList& a, const uint32_t* h_bits) {
-  return dig != nullptr ? write_u<NT, T, true>(d, p, fresh, sel, bm, dig, rr, g, tiling, unroll,
-                                               grid, lds, s, a, h_bits)
-                        : write_u<NT, T, false>(d, p, fresh, sel, bm, dig, rr, g, tiling, unroll,
-                                                grid, lds, s, a, h_bits);
-}
-
-}  // namespace
-
 hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
                         const uint8_t* d_bitmap, uint64_t* d_digests, const Geometry& g_class,
                         const LaunchShape& ls, int tiling, uint64_t offset, uint64_t len,
@@ -2515,11 +2234,8 @@ hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const v
   if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs ||
       tiling < kUpdateClassTiles || tiling > kUpdateArgListTiles)
     return hipErrorInvalidValue;
-  Geometry g = g_class;
-  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
-  g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;  // chunks of the range
-  g.total_tiles = (tiling == kUpdateClassTiles ? g.S * g.m : n_items) * g.tiles_per_block;
-  g.rot = 0;
+  const Geometry g = range_geometry(
+      g_class, ls, len, tiling == kUpdateClassTiles ? g_class.S * g_class.m : n_items);
   if (g.total_tiles == 0) return hipSuccess;
   if (g.k > 256 && tiling != kUpdateClassTiles) return hipErrorInvalidValue;
   if (tiling == kUpdateArgListTiles &&
@@ -2528,21 +2244,33 @@ hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const v
   if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
   if (tiling == kUpdateClassTiles && g.gate == nullptr) return hipErrorInvalidValue;
   const ReadRange rr{offset, len};
-  const ArgList a{h_items, n_items};
   uint8_t* d = static_cast<uint8_t*>(d_data);
   uint8_t* p = static_cast<uint8_t*>(d_parity);
   const uint8_t* f = static_cast<const uint8_t*>(d_new);
   const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
   const uint32_t lds = ls.lds_bytes;
-  if (ls.threads == 256)
-    return ls.nt ? write_dig<true, 256>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
-                                        ls.unroll, grid, lds, s, a, h_bits)
-                 : write_dig<false, 256>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
-                                         ls.unroll, grid, lds, s, a, h_bits);
-  return ls.nt ? write_dig<true, 64>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling, ls.unroll,
-                                     grid, lds, s, a, h_bits)
-               : write_dig<false, 64>(d, p, f, d_sel, d_bitmap, d_digests, rr, g, tiling,
-                                      ls.unroll, grid, lds, s, a, h_bits);
+  return with_shape(ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    return with_bool(d_digests != nullptr, [&](auto dig) {
+      constexpr bool DIG = decltype(dig)::value;
+      switch (tiling) {
+        case kUpdateArgListTiles:
+          return with_capacity(n_items, [&](auto cap) {
+            constexpr uint32_t CAP = decltype(cap)::value;  // and two bits per item
+            return launch_codec(write_arglist_kernel<U, NT, T, DIG, CAP>, grid, T, lds, s, d, p, f,
+                                d_digests, rr, g, arg_items<CAP>(h_items, n_items),
+                                arg_items<CAP / 16>(h_bits, (n_items + 15) / 16));
+          });
+        case kUpdateListTiles:
+          return launch_codec(write_list_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, f,
+                              static_cast<const uint32_t*>(d_sel), d_digests, rr, g);
+        default:
+          return launch_codec(write_class_kernel<U, NT, T, DIG>, grid, T, lds, s, d, p, f,
+                              static_cast<const uint8_t*>(d_sel), d_bitmap, d_digests, rr, g);
+      }
+    });
+  });
 }
 
 hipError_t launch_write_check(const uint8_t* d_bitmap, const uint8_t* d_mask, const Geometry& g,

@@ -5,7 +5,7 @@ The per-operation files (test_gpu_repair, test_gpu_verify, test_gpu_update,
 test_gpu_digest, test_gpu_read) share one small grid.  This file crosses what
 that grid leaves out:
 
-* every member count XEC_NM_SWITCH (csrc/xec_kernels.hip) compiles -- 1, 2, 4,
+* every member count with_shape (csrc/xec_dispatch.h) compiles -- 1, 2, 4,
   8, 16, 32 -- and the generic loop below 8, at whole groups of 8 and at groups
   plus a tail;
 * every (threads, unroll) pair at block sizes whose tiles come out full, cut
@@ -138,12 +138,12 @@ def overrides_for(ti, si):
 
 
 def compiled_member_counts():
-    """The case labels of XEC_NM_SWITCH, from the source."""
-    text = (CSRC / "xec_kernels.hip").read_text()
-    body = text[text.index("#define XEC_NM_SWITCH"):]
+    """The case labels of with_shape's member-count switch, from the source."""
+    text = (CSRC / "xec_dispatch.h").read_text()
+    body = text[text.index("switch (nm) {"):]
     body = body[: body.index("default:")]
     cases = [int(x) for x in re.findall(r"case (\d+):", body)]
-    assert [int(x) for x in re.findall(r"NM = (\d+);", body)] == cases
+    assert [int(x) for x in re.findall(r"with_shape<(\d+)>", body)] == cases
     return cases
 
 

@@ -355,11 +355,17 @@ def test_coverage_without_a_device():
                     kernels.index("constexpr int kWriteDelta")]
     write = kernels[kernels.index("constexpr int kWriteDelta"):
                     kernels.index("hipError_t launch_write_check")]
-    # both launchers count the chunks of the RANGE; a lane's granule takes part while below `end`
+    # both launchers count the chunks of the RANGE, through the one helper that does; a lane's
+    # granule takes part while below `end`
+    helper = kernels[kernels.index("Geometry range_geometry("):
+                     kernels.index("hipError_t launch_encode(")]
+    assert kernels.count("g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;") == 1
+    assert helper.count("g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;") == 1
+    assert helper.count("const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * "
+                        "(uint64_t)ls.unroll;") == 1
     for part in (patch, write):
-        assert part.count("g.tiles_per_block = (len + tile_bytes - 1) / tile_bytes;") == 1
-        assert part.count("const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * "
-                          "(uint64_t)ls.unroll;") == 1
+        assert part.count("const Geometry g = range_geometry(") == 1
+        assert part.count("g.tiles_per_block =") == 0 and part.count("tile_bytes") == 0
     # every load, fold, digest term and store of a granule is guarded, and by nothing else
     assert patch.count("if (off + u * kStep < end)") == 9
     assert patch.count("for (int u = 0; u < U; ++u)") == 9

@@ -26,6 +26,23 @@ def test_scan_fuzz_asan_ubsan(tmp_path):
     assert "scan_fuzz ok" in p.stdout
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_dispatch_map_asan_ubsan(tmp_path):
+    """The launch dispatcher (csrc/xec_dispatch.h) hands its callable the tag
+    whose constants equal the run-time shape, and the capacity that holds the
+    list: the one thing no GPU test can see, since the generic kernel or the
+    other cache policy computes the same bytes."""
+    exe = tmp_path / "dispatch_map"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{ROOT / 'erasure-code-benchmark_amd' / 'csrc'}",
+                    str(ROOT / "tests" / "host" / "dispatch_map.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True)
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    assert "dispatch_map ok" in p.stdout
+
+
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="needs gcc")
 def test_oracle_asan_ubsan(tmp_path):
     """The oracle itself (the parity checker) under ASan/UBSan: known answers

@@ -11,35 +11,18 @@
 from __future__ import annotations
 
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG_DIR
-
-ASM = PKG_DIR / "build" / "xec_kernels-gfx950.s"
+import isa_listing
+from isa_listing import nt as _nt
 
 
 @pytest.fixture(scope="module")
 def kernels() -> dict[str, dict]:
-    subprocess.run(["make", "-C", str(PKG_DIR), "asm"], check=True, capture_output=True)
-    text = ASM.read_text()
-    out = {}
-    for m in re.finditer(r"^(_ZN3xec[12][0-9](encode|decode)_(?:class_|list_|arglist_|argmask_|devlist_)?kernel\w+):.*?^\s*s_endpgm", text,
-                         re.S | re.M):
-        out[m.group(1)] = {"body": m.group(0)}
-    meta = re.findall(r"\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)", text, re.S)
-    for name, block, vgpr in meta:
-        if name in out:
-            out[name]["vgpr"] = int(vgpr)
-            out[name]["sgpr"] = int(re.search(r"\.sgpr_count:\s+(\d+)", block).group(1))
+    out = isa_listing.kernels("(?:encode|decode)(?:_class|_list|_arglist|_argmask|_devlist)?")
     assert len(out) >= 100, "kernel instantiations not found in the ISA"
     return out
-
-
-def _nt(name: str) -> bool:
-    # template args <NM, U, NT, T>: ...ILi16ELi1ELb1ELi64E...
-    return re.search(r"ELb1E", name) is not None
 
 
 def test_nt_kernels_carry_their_cache_policy(kernels):

@@ -13,45 +13,21 @@ cross-compiles; the listing is `make asm`'s, as tests/test_isa.py reads it).
 from __future__ import annotations
 
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG_DIR
+import isa_listing
+from isa_listing import loads16 as _loads16, nt as _nt, stores16 as _stores16
 
-ASM = PKG_DIR / "build" / "xec_kernels-gfx950.s"
 KINDS = ["repair_list", "repair_arglist", "repair_class", "verify"]
 
 
 @pytest.fixture(scope="module")
 def kernels() -> dict[str, dict]:
-    subprocess.run(["make", "-C", str(PKG_DIR), "asm"], check=True, capture_output=True)
-    text = ASM.read_text()
-    out = {}
-    for m in re.finditer(r"^(_ZN3xec[12][0-9](?:repair_list|repair_arglist|repair_class|verify)"
-                         r"_kernel\w+):.*?^\s*s_endpgm", text, re.S | re.M):
-        out[m.group(1)] = {"body": m.group(0)}
-    meta = re.findall(r"\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)", text, re.S)
-    for name, block, vgpr in meta:
-        if name in out:
-            out[name]["vgpr"] = int(vgpr)
-            out[name]["sgpr"] = int(re.search(r"\.sgpr_count:\s+(\d+)", block).group(1))
+    out = isa_listing.kernels("|".join(KINDS))
     # 7 member counts x 2 unrolls x 2 policies x 2 workgroup sizes, arglist x 3 capacities
     assert len(out) == 56 * 6, f"{len(out)} repair / verify instantiations in the ISA"
     return out
-
-
-def _nt(name: str) -> bool:
-    # template args <NM, U, NT, T>: ...ILi16ELi1ELb1ELi64E...
-    return re.search(r"ELb1E", name) is not None
-
-
-def _loads16(body):
-    return re.findall(r"^\s*((?:global|buffer)_load_dwordx4[^\n]*)", body, re.M)
-
-
-def _stores16(body):
-    return re.findall(r"^\s*((?:global|buffer|flat|scratch)_store_dwordx4[^\n]*)", body, re.M)
 
 
 def test_nt_instantiations_load_nt(kernels):

@@ -17,40 +17,21 @@ read it).
 from __future__ import annotations
 
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG_DIR
+import isa_listing
+from isa_listing import loads16 as _loads16, nt as _nt, stores16 as _stores16
 
-ASM = PKG_DIR / "build" / "xec_kernels-gfx950.s"
 KINDS = {"update_list": 8, "update_arglist": 24, "update_class": 8}
 
 
 @pytest.fixture(scope="module")
 def kernels() -> dict[str, dict]:
-    subprocess.run(["make", "-C", str(PKG_DIR), "asm"], check=True, capture_output=True)
-    text = ASM.read_text()
-    out = {}
-    for m in re.finditer(r"^(_ZN3xec[12][0-9](?:update_list|update_arglist|update_class)"
-                         r"_kernel\w+):.*?^\s*s_endpgm", text, re.S | re.M):
-        out[m.group(1)] = {"body": m.group(0)}
+    out = isa_listing.kernels("|".join(KINDS))
     # 2 unrolls x 2 policies x 2 workgroup sizes, arglist x 3 capacities; no member count
     assert len(out) == sum(KINDS.values()), f"{len(out)} update instantiations in the ISA"
     return out
-
-
-def _nt(name: str) -> bool:
-    # template args <U, NT, T>: ...ILi1ELb1ELi64E...
-    return re.search(r"ELb1E", name) is not None
-
-
-def _loads16(body):
-    return re.findall(r"^\s*((?:global|buffer)_load_dwordx4[^\n]*)", body, re.M)
-
-
-def _stores16(body):
-    return re.findall(r"^\s*((?:global|buffer|flat|scratch)_store_dwordx4[^\n]*)", body, re.M)
 
 
 def test_instantiation_count_is_the_template_set(kernels):

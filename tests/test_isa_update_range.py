@@ -15,24 +15,18 @@ Nothing else about the instruction stream is looked at.
 from __future__ import annotations
 
 import re
-import subprocess
 
 import pytest
 
-from conftest import PKG_DIR
+import isa_listing
+from isa_listing import atomic_adds as _atomic_adds, loads16 as _loads16, stores16 as _stores16
 
-ASM = PKG_DIR / "build" / "xec_kernels-gfx950.s"
 KINDS = {"patch_list": 16, "patch_arglist": 48, "patch_class": 16}
 
 
 @pytest.fixture(scope="module")
 def kernels() -> dict[str, str]:
-    subprocess.run(["make", "-C", str(PKG_DIR), "asm"], check=True, capture_output=True)
-    text = ASM.read_text()
-    out = {}
-    for m in re.finditer(r"^(_ZN3xec[12][0-9](?:patch_list|patch_arglist|patch_class)"
-                         r"_kernel\w+):.*?^\s*s_endpgm", text, re.S | re.M):
-        out[m.group(1)] = m.group(0)
+    out = {n: k["body"] for n, k in isa_listing.kernels("|".join(KINDS)).items()}
     assert len(out) == sum(KINDS.values()), f"{len(out)} ranged-update instantiations in the ISA"
     return out
 
@@ -42,18 +36,6 @@ def _targs(name: str):
     m = re.search(r"_kernelILi([12])ELb([01])ELi(64|256)ELb([01])E", name)
     assert m, name
     return int(m.group(1)), m.group(2) == "1", int(m.group(3)), m.group(4) == "1"
-
-
-def _loads16(body):
-    return re.findall(r"^\s*((?:global|buffer)_load_dwordx4[^\n]*)", body, re.M)
-
-
-def _stores16(body):
-    return re.findall(r"^\s*((?:global|buffer|flat|scratch)_store_dwordx4[^\n]*)", body, re.M)
-
-
-def _atomic_adds(body):
-    return re.findall(r"^\s*((?:global|flat|buffer)_atomic_add\w*[^\n]*)", body, re.M)
 
 
 def test_instantiation_count_is_the_template_set(kernels):

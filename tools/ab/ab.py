@@ -173,6 +173,14 @@ def main():
         e, d = statistics.median(r["enc"]), statistics.median(r["dec"])
         out["libs"][n] = {"enc_ms_med": round(e, 4), "enc_GBps": round(b_enc / e / 1e6, 1),
                           "dec_ms_med": round(d, 4), "dec_GBps": round(b_dec / d / 1e6, 1)}
+        # each round's own median and their spread, (max - min) / median: what this arm
+        # moves by from round to round, the margin another arm's median is read against
+        for op in ("enc", "dec"):
+            per_round = [statistics.median(r[op][i:i + args.iters])
+                         for i in range(0, len(r[op]), args.iters)]
+            out["libs"][n][f"{op}_round_ms"] = [round(x, 4) for x in per_round]
+            out["libs"][n][f"{op}_spread"] = round(
+                (max(per_round) - min(per_round)) / statistics.median(per_round), 4)
         print(n, out["libs"][n], flush=True)
     if args.out:
         Path(args.out).write_text(json.dumps(out, indent=1))
