@@ -1572,6 +1572,151 @@ xec_status xec_read_device(const void* d_data, const void* d_parity, size_t S, s
   return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
 }
 
+// ---- vectored degraded read --------------------------------------------------------
+// xec_readv / xec_readv_device: xec_read with a range per entry.  The tile
+// schedule is a table (xec_internal.h, xec_plan_readv) instead of a division:
+// entry t owns tiles [tile[t], tile[t + 1]) and bytes [out[t], out[t + 1]) of
+// d_out, and a tile finds its entry by binary search (xec_kernels.hip, vectored
+// read).  Residency as xec_read (read_occupancy).
+static thread_local int g_readv_tiling_used = 0;  // xec_readv_tiling_used: this thread's last readv
+
+static xec_status readv_check_batch(size_t S, size_t bs, size_t k, size_t m) {
+  if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes || (uint64_t)bs >= (1ull << 32))
+    return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+static xec_status readv_impl(const void* d_data, const void* d_parity, size_t S, size_t bs,
+                             size_t k, size_t m, const uint8_t* h_bitmap, const xec_iov* h_iov,
+                             size_t n, void* d_out, size_t out_bytes, void* d_scratch,
+                             size_t scratch_bytes, hipStream_t stream) {
+  g_readv_tiling_used = 0;
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (n == 0 || S == 0) return XEC_SUCCESS;
+  st = readv_check_batch(S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (d_out == nullptr || h_iov == nullptr) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return XEC_INVALID_ALIGNMENT;
+  // The tile size is the launch shape's; the residency, which needs the plan's
+  // loss count, is set once the plan is known.
+  xec::LaunchShape ls = launch_shape(bs, 0);
+  const size_t tile_bytes = 16 * (size_t)ls.threads * (size_t)ls.unroll;
+  // Six words per entry: 256 entries are 6 KiB of kernel arguments, 1,024 would
+  // ship 24 KiB with every launch.
+  const bool in_args = n <= xec::kReadvArgEntries;
+  const size_t cap = in_args ? xec::readv_capacity(n) : n;
+  uint32_t short_table[xec_readv_table_words(xec::kReadvArgEntries)];
+  XecReadvPlan plan;
+  (void)xec_plan_readv(h_bitmap, S, bs, k, m, h_iov, n, tile_bytes, cap,
+                       in_args ? short_table : nullptr, &plan);
+  if (plan.range_status != XEC_SUCCESS) return plan.range_status;
+  if (plan.total_bytes > out_bytes || plan.total_tiles > 0xFFFFFFFFull ||
+      ranges_overlap(d_out, plan.total_bytes, d_data, S * k * bs) ||
+      ranges_overlap(d_out, plan.total_bytes, d_parity, S * m * bs))
+    return XEC_INVALID_SIZE;
+  if (plan.items_status != XEC_SUCCESS) return plan.items_status;
+  if (!in_args) {
+    st = check_scratch(d_scratch, scratch_bytes, xec_readv_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  ls = launch_shape(bs, read_occupancy(k / m, plan.n_lost));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_readv_tiling_used = XEC_TILING_ARG_LIST;
+    return launch_status(__LINE__,
+                         xec::launch_readv(d_data, d_parity, d_out, g, ls, xec::kReadArgListTiles, n,
+                                           plan.total_tiles, nullptr, short_table, stream));
+  }
+  return upload_list_and_launch(
+      xec_readv_scratch_bytes(n), d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        (void)xec_plan_readv(h_bitmap, S, bs, k, m, h_iov, n, tile_bytes, n, staged, nullptr);
+        g_readv_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_readv(d_data, d_parity, d_out, g, ls, xec::kReadListTiles, n,
+                                 plan.total_tiles, static_cast<const uint32_t*>(d_scratch), nullptr,
+                                 stream);
+      });
+}
+
+xec_status xec_readv(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                     size_t m, const uint8_t* h_bitmap, const xec_iov* h_iov, size_t n_items,
+                     void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes,
+                     hipStream_t stream) {
+  return guarded([&] {
+    return readv_impl(d_data, d_parity, S, bs, k, m, h_bitmap, h_iov, n_items, d_out, out_bytes,
+                      d_scratch, scratch_bytes, stream);
+  });
+}
+
+size_t xec_readv_scratch_bytes(size_t n_items) { return 4 * xec_readv_table_words(n_items); }
+
+size_t xec_readv_device_work_bytes(size_t n_items) {
+  return n_items ? (4 * xec::readv_work_words(n_items) + 7) / 8 * 8 : 0;
+}
+
+int xec_readv_tiling_used(void) { return g_readv_tiling_used; }
+
+xec_status xec_readv_device(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                            size_t m, const uint8_t* d_bitmap, const xec_iov* d_iov,
+                            size_t n_items, void* d_out, size_t out_bytes, void* d_work,
+                            size_t work_bytes, int32_t* d_status, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_readv_tiling_used = 0;
+  xec_status st = check_entry(d_data, d_parity, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (n_items == 0 || S == 0)
+    return hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) == hipSuccess ? XEC_SUCCESS
+                                                                              : XEC_DEVICE_ERROR;
+  st = readv_check_batch(S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (d_out == nullptr || d_iov == nullptr || d_work == nullptr) return XEC_INVALID_SIZE;
+  if (work_bytes < xec_readv_device_work_bytes(n_items)) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0 || reinterpret_cast<uintptr_t>(d_iov) % 4 != 0 ||
+      reinterpret_cast<uintptr_t>(d_work) % 8 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (ranges_overlap(d_out, out_bytes, d_data, S * k * bs) ||
+      ranges_overlap(d_out, out_bytes, d_parity, S * m * bs))
+    return XEC_INVALID_SIZE;
+  // the most tiles an entry can have is at the smallest tile, 1 KiB
+  if ((uint64_t)n_items > 0xFFFFFFFFull / (((uint64_t)bs + 1023) / 1024)) return XEC_INVALID_SIZE;
+  const StreamDevice sd(stream);
+  if (!sd.ok()) return XEC_DEVICE_ERROR;
+  // No host view of the bitmap: the table of a reconstruct tile (read_occupancy).
+  xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, d_bitmap ? 1 : 0));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  // The totals are known only on the device, so the read kernel walks them with
+  // a grid fixed at launch from the most tiles out_bytes and n_items admit (an
+  // entry's last tile may be a partial one), clamped as xec_decode_device_list
+  // clamps its grid.
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  const uint64_t bound = (uint64_t)out_bytes / tile_bytes + n_items;
+  if (ls.max_grid == 0) {
+    const uint64_t resident = resident_workgroups(ls);
+    if (resident == 0) return XEC_DEVICE_ERROR;
+    const uint64_t want = bound / 8 < kDevListMaxGrid ? bound / 8 : kDevListMaxGrid;
+    ls.max_grid = (uint32_t)(want > resident ? want : resident);
+  }
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  uint32_t* work = static_cast<uint32_t*>(d_work);
+  const uint32_t* iov = reinterpret_cast<const uint32_t*>(d_iov);
+  if (xec::launch_readv_check(d_bitmap, iov, n_items, g, tile_bytes, work, d_status, stream) !=
+          hipSuccess ||
+      xec::launch_readv_scan(work, n_items, out_bytes, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  g_readv_tiling_used = XEC_TILING_LIST;
+  const hipError_t le = xec::launch_readv(d_data, d_parity, d_out, g, ls, xec::kReadDevTiles, n_items,
+                                          bound, iov, nullptr, stream, d_bitmap, work);
+  return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
+}
+
 // ---- ranged update with digest upkeep ------------------------------------------------
 // xec_update_range / xec_update_range_device: xec_update over bytes
 // [offset, offset + len) of each named block, and with d_digests the stored

@@ -69,4 +69,14 @@ auto with_capacity(uint64_t n, F&& f) {
   }
 }
 
+// The vectored read's table is six words per entry where the lists above are
+// one: its capacities stop at 256 entries (6 KiB of arguments).
+inline uint32_t readv_capacity(uint64_t n) { return n <= 64 ? 64 : 256; }
+
+template <class F>
+auto with_readv_capacity(uint64_t n, F&& f) {
+  if (readv_capacity(n) == 64) return f(std::integral_constant<uint32_t, 64>{});
+  return f(std::integral_constant<uint32_t, 256>{});
+}
+
 }  // namespace xec

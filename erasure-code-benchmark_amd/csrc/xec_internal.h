@@ -73,6 +73,48 @@ xec_status xec_scan_read_items(const uint8_t* bm, size_t S, size_t k, size_t m,
                                const uint32_t* items, size_t n_items, uint32_t* lost_bits,
                                size_t* n_lost);
 
+// Vectored read plan (xec_readv, xec_check_readv): the verdict over n entries
+// that each bring their own range, and the table the readv kernels walk
+// (xec_kernels.hip).  A tile is (entry, chunk of tile_bytes of the entry's
+// range), tile_bytes = 16 * threads * unroll of the call's launch shape.
+//
+// The table is u32 words in six columns of `cap` >= n entries each, so that
+// the copy in the kernel arguments (cap = the compiled capacity) and the
+// uploaded one (cap = n) are read by the same code:
+//   [0, cap]                 tile start: exclusive prefix of ceil(len / tile_bytes),
+//                            word n = the total (n + 1 values; the rest 0)
+//   [cap + 1, 2 cap + 1)     item   c << 8 | i
+//   [2 cap + 1, 3 cap + 1)   offset
+//   [3 cap + 1, 4 cap + 1)   len
+//   [4 cap + 1, 5 cap + 1)   output start, low word   (exclusive prefix of len)
+//   [5 cap + 1, 6 cap + 1)   output start, high word
+//   [6 cap + 1, + ceil(cap / 32))  bit t of word t / 32 = entry t is lost
+// xec_readv_table_words(cap) words in all; columns past n are zeroed.
+constexpr size_t xec_readv_table_words(size_t cap) {
+  return cap ? 6 * cap + 1 + (cap + 31) / 32 : 0;
+}
+
+struct XecReadvPlan {
+  xec_status range_status = XEC_SUCCESS;  // XEC_INVALID_SIZE if an entry has len == 0, offset or
+                                          // len % 16 != 0, or offset + len > bs (64-bit sum)
+  xec_status items_status = XEC_SUCCESS;  // else XEC_INVALID_COUNTS (c >= S or i >= k + m), else
+                                          // XEC_DECODE_FAILURE (xec_scan_read_items' rule)
+  size_t n_lost = 0;          // entries that need a reconstruction, a repeat counted each time
+  uint64_t total_bytes = 0;   // sum of len
+  uint64_t total_tiles = 0;   // sum of ceil(len / tile_bytes); may pass 32 bits (the table's
+                              // tile column is then truncated and must not be used)
+};
+
+// Returns the first of range_status and items_status that is not success (k, m
+// invalid as xec_check_args, or iov null with n > 0: XEC_INVALID_COUNTS with
+// both fields set to it).  The totals are valid when range_status is success,
+// n_lost and the table when the return value is.  `table` may be null (verdict
+// and totals only); else it holds xec_readv_table_words(cap) words, cap >= n.
+// tile_bytes > 0.  Defined in xec_scan.cpp.
+xec_status xec_plan_readv(const uint8_t* bm, size_t S, size_t bs, size_t k, size_t m,
+                          const xec_iov* iov, size_t n, size_t tile_bytes, size_t cap,
+                          uint32_t* table, XecReadvPlan* plan);
+
 // Write scan (xec_write; xec_check_write_items is this with bits null): the
 // verdict over the n_items WRITTEN items c << 8 | i, i < k, strictly ascending.
 // XEC_INVALID_COUNTS if any item breaks xec_update's item rules (i >= k,

@@ -258,6 +258,40 @@ hipError_t launch_read(const void* d_data, const void* d_parity, void* d_out, co
 // of its class lost too).  The caller zeroes *d_status first, stream-ordered.
 hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
                              const Geometry& g, int32_t* d_status, hipStream_t s);
+// Vectored read (xec_readv, xec_readv_device): launch_read with a range and an
+// output start per entry.  A tile is (entry, chunk of the entry's range), and
+// entry e owns tiles [tile[e], tile[e + 1]); n entries, n < 2^32.  Of g only S,
+// k, m, nm, bs and gate are used.  Where the schedule comes from:
+//   kReadArgListTiles  h_table = the table of xec_plan_readv (xec_internal.h)
+//                      laid out for cap = readv_capacity(n), by value in the
+//                      kernel arguments, n <= kReadvArgEntries;
+//   kReadListTiles     d_table = the same table laid out for cap = n,
+//                      xec_readv_table_words(n) words;
+//   kReadDevTiles      d_table = the n entries themselves (xec_iov: item,
+//                      offset, len), d_bitmap = the batch bitmap or nullptr,
+//                      d_work = readv_work_words(n) words, 8-byte aligned: n + 1
+//                      64-bit output starts, then n + 1 tile starts, [n] = the
+//                      totals (launch_readv_check, then launch_readv_scan);
+//                      g.gate set.
+// `tiles` sizes the grid (with ls.max_grid): the total of the table, or for
+// kReadDevTiles the most the device's total can be.
+constexpr uint64_t kReadvArgEntries = 256;  // the largest capacity (xec_dispatch.h)
+inline uint64_t readv_work_words(uint64_t n) { return 3 * (n + 1); }
+hipError_t launch_readv(const void* d_data, const void* d_parity, void* d_out, const Geometry& g,
+                        const LaunchShape& ls, int tiling, uint64_t n, uint64_t tiles,
+                        const uint32_t* d_table, const uint32_t* h_table, hipStream_t s,
+                        const uint8_t* d_bitmap = nullptr, const uint32_t* d_work = nullptr);
+// xec_readv_device's verdict and schedule.  Check: *d_status = max over the n
+// entries of 0 (servable), 1 (a broken range), 3 (c >= S or i >= k + m) and 4
+// (not servable), and each entry's length and tile count (of tile_bytes) into
+// d_work.  Scan: those into exclusive prefixes in list order with the totals at
+// [n], and *d_status raised to 1 if the bytes exceed out_bytes.  The caller
+// zeroes *d_status first, stream-ordered.
+hipError_t launch_readv_check(const uint8_t* d_bitmap, const uint32_t* d_iov, uint64_t n,
+                              const Geometry& g, uint64_t tile_bytes, uint32_t* d_work,
+                              int32_t* d_status, hipStream_t s);
+hipError_t launch_readv_scan(uint32_t* d_work, uint64_t n, uint64_t out_bytes, int32_t* d_status,
+                             hipStream_t s);
 // Ranged update (xec_update_range, xec_update_range_device): launch_update over
 // bytes [offset, offset + len) of each named block only, tilings and d_sel /
 // h_items as there (kUpdate*Tiles); a tile is (list position or class, chunk of

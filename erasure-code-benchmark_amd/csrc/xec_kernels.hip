@@ -30,6 +30,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "xec_internal.h"
 #include "xec_kernels.h"
 
 namespace xec {
@@ -1570,6 +1571,300 @@ hipError_t launch_read_check(const uint8_t* d_bitmap, const uint32_t* d_items, u
   if (n == 0) return hipSuccess;
   return launch(read_check_kernel, grid_for((n + 255) / 256, 8192, 256), 256, 0, s, d_bitmap,
                 d_items, n, g, d_status);
+}
+
+// ---------------------------------------------------------------------------
+// vectored read (xec_readv, xec_readv_device).  Kernels and launchers together.
+//
+// The degraded read above with a range per entry.  Entries differ in their
+// number of chunks, so a tile is no longer (t / tiles_per_block, t %
+// tiles_per_block): entry e owns tiles [tile[e], tile[e + 1]), an exclusive
+// prefix the host plan (xec_internal.h) or the scan kernel below wrote, and
+// tile t finds e by binary search over it -- ceil(log2 n) dependent scalar
+// loads from the kernel arguments, the uploaded table or d_work.  The entry,
+// its range, its output start and its verdict are scalar too, so they are
+// uniform per workgroup and the copy / reconstruct branch stays wave-uniform.
+// The tile itself is read_tile_to: the bounds argument above read_tile holds
+// per entry -- the slot is out + the entry's output start and no pointer below
+// it is formed, the ragged-tail predicate uses the entry's offset + len, and
+// the NT store's buffer resource is the entry's len bytes long.  st16_slot
+// takes (int)len: the NT kernels run only for bs < 2^31 (launch_shape in
+// xec_api.cpp), and len <= bs, so the cast never changes the value; for larger
+// blocks the plain-store kernels run and len is not used at all.
+// Tiles are walked from the end of the list, grid-stride, as read_list_kernel.
+// ---------------------------------------------------------------------------
+
+// read_tile with the slot as an argument.  A copy and not read_tile's body, as
+// xor_members_to above: with read_tile forwarding to this, 180 of the 280 read
+// kernels came out with another instruction schedule, and those kernels stay
+// instruction for instruction what they were.
+template <int NM, int U, bool NT, int T>
+__device__ __forceinline__ void read_tile_to(const uint8_t* __restrict__ data,
+                                             const uint8_t* __restrict__ parity, uint8_t* slot,
+                                             uint32_t item, bool lost, uint64_t chunk,
+                                             const ReadRange& rr, const Geometry& g) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint32_t m = (uint32_t)g.m, k = (uint32_t)g.k;
+  const uint64_t c = item >> 8;
+  const uint32_t i = item & 0xFFu;
+  const uint64_t end = rr.offset + rr.len;
+  const uint64_t off = rr.offset + (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+  const uint32_t len = (uint32_t)rr.len;
+  auto store = [&](uint64_t o, u32x4 v) { st16_slot<NT>(slot, len, o - rr.offset, v); };
+  if (!lost) {
+    const uint8_t* blk = i < k ? data + (c * g.k + i) * g.bs : parity + (c * g.m + (i - k)) * g.bs;
+    u32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (off + u * kStep < end) v[u] = ld16<NT>(blk + off + u * kStep);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (off + u * kStep < end) store(off + u * kStep, v[u]);
+    return;
+  }
+  const uint32_t j = i < k ? i % m : i - k;  // the entry's class
+  const uint8_t* base = data + (c * g.k + j) * g.bs;
+  if (i < k)  // a data block: the other members and the class parity, as decode
+    xor_members_to<NM, U, NT, T>(base, g.m * g.bs, parity + (c * g.m + j) * g.bs, (int)(i / m), off,
+                                 end, nm, store);
+  else  // a parity block: every data member, as encode
+    xor_members_to<NM, U, NT, T>(base, g.m * g.bs, nullptr, -1, off, end, nm, store);
+}
+
+// The entry whose tiles [tile(e), tile(e + 1)) hold t; t < tile(n), and every
+// entry has at least one tile, so the prefix is strictly increasing.
+template <typename TileAt>
+__device__ __forceinline__ uint32_t readv_find(TileAt tile, uint32_t n, uint32_t t) {
+  uint32_t lo = 0, hi = n;  // tile(lo) <= t < tile(hi)
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (tile(mid) <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// The table of xec_internal.h (xec_plan_readv) in columns of `cap` entries;
+// w(x) is word x of it, a scalar load.
+template <int NM, int U, bool NT, int T, typename W>
+__device__ __forceinline__ void readv_table_tiles(const uint8_t* __restrict__ data,
+                                                  const uint8_t* __restrict__ parity, uint8_t* out,
+                                                  W w, uint32_t n, uint64_t cap,
+                                                  const Geometry& g) {
+  const uint32_t total = w(n);
+  for (uint64_t t0 = blockIdx.x; t0 < total; t0 += gridDim.x) {
+    const uint32_t t = total - 1 - (uint32_t)t0;
+    const uint32_t e = readv_find(w, n, t);
+    const uint64_t col = cap + 1 + e;  // the entry's word of the first column past the tiles
+    const ReadRange rr{w(col + cap), w(col + 2 * cap)};
+    const uint64_t start = (uint64_t)w(col + 4 * cap) << 32 | w(col + 3 * cap);
+    const bool lost = ((w(6 * cap + 1 + (e >> 5)) >> (e & 31u)) & 1u) != 0;
+    read_tile_to<NM, U, NT, T>(data, parity, out + start, w(col), lost, t - w(e), rr, g);
+  }
+}
+
+// The table in device memory (cap = n).
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void readv_list_kernel(const uint8_t* __restrict__ data,
+                                                       const uint8_t* __restrict__ parity,
+                                                       uint8_t* out,
+                                                       const uint32_t* __restrict__ table,
+                                                       uint32_t n, Geometry g) {
+  readv_table_tiles<NM, U, NT, T>(
+      data, parity, out, [&](uint64_t x) { return *(const_u32_as4)(table + x); }, n, n, g);
+}
+
+// The same with the table in the kernel arguments (at most CAP entries).
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void readv_arglist_kernel(const uint8_t* __restrict__ data,
+                                                          const uint8_t* __restrict__ parity,
+                                                          uint8_t* out, uint32_t n, Geometry g,
+                                                          ArgItems<xec_readv_table_words(CAP)> table) {
+  readv_table_tiles<NM, U, NT, T>(
+      data, parity, out, [&](uint64_t x) { return table.v[x]; }, n, CAP, g);
+}
+
+// Entries and bitmap on the device (xec_readv_device; gated on the verdict of
+// readv_check_kernel and readv_scan_kernel, so every entry it sees is valid,
+// in range and servable, and the output fits).  work = d_work (xec_kernels.h
+// readv_work_words): the 64-bit output starts, then the tile starts; item,
+// range and the block's bitmap byte are scalar loads.
+template <int NM, int U, bool NT, int T>
+__global__ __launch_bounds__(T) void readv_dev_kernel(const uint8_t* __restrict__ data,
+                                                      const uint8_t* __restrict__ parity,
+                                                      uint8_t* out,
+                                                      const uint32_t* __restrict__ iov,
+                                                      const uint8_t* __restrict__ bitmap,
+                                                      const uint32_t* __restrict__ work,
+                                                      uint32_t n, Geometry g) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  const uint32_t* tiles = work + 2 * ((uint64_t)n + 1);
+  auto tile = [&](uint32_t x) { return *(const_u32_as4)(tiles + x); };
+  const uint32_t total = tile(n);
+  for (uint64_t t0 = blockIdx.x; t0 < total; t0 += gridDim.x) {
+    const uint32_t t = total - 1 - (uint32_t)t0;
+    const uint32_t e = readv_find(tile, n, t);
+    const uint32_t* ent = iov + 3 * (uint64_t)e;
+    const uint32_t item = *(const_u32_as4)ent;
+    const ReadRange rr{*(const_u32_as4)(ent + 1), *(const_u32_as4)(ent + 2)};
+    const uint64_t start = (uint64_t) * (const_u32_as4)(work + 2 * (uint64_t)e + 1) << 32 |
+                           *(const_u32_as4)(work + 2 * (uint64_t)e);
+    const bool lost =
+        bitmap != nullptr && sbyte(reinterpret_cast<uint64_t>(bitmap) +
+                                   (uint64_t)(item >> 8) * (g.k + g.m) + (item & 0xFFu)) == 0;
+    read_tile_to<NM, U, NT, T>(data, parity, out + start, item, lost, t - tile(e), rr, g);
+  }
+}
+
+// One thread per entry: *status = max(*status, verdict), verdict 0 servable,
+// 1 a range that breaks the rules (len == 0, offset or len % 16, offset + len
+// > bs), 3 c >= S or i >= k + m, 4 lost with another block of its class lost
+// too; an entry with a nonzero verdict is not dereferenced beyond its own 12
+// bytes.  Writes the entry's length into bytes[e] and its tile count into
+// tiles[e] (0 and 0 for a broken range) for readv_scan_kernel.
+__global__ __launch_bounds__(256) void readv_check_kernel(const uint8_t* __restrict__ bitmap,
+                                                         const uint32_t* __restrict__ iov,
+                                                         uint64_t n, Geometry g,
+                                                         uint64_t tile_bytes, uint64_t* bytes,
+                                                         uint32_t* tiles, int32_t* status) {
+  const uint64_t row = g.k + g.m;
+  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n;
+       t += (uint64_t)gridDim.x * 256) {
+    const uint32_t item = iov[3 * t];
+    const uint64_t offset = iov[3 * t + 1], len = iov[3 * t + 2];
+    const bool range_ok = len != 0 && offset % 16 == 0 && len % 16 == 0 && offset + len <= g.bs;
+    bytes[t] = range_ok ? len : 0;
+    tiles[t] = range_ok ? (uint32_t)((len + tile_bytes - 1) / tile_bytes) : 0;
+    const uint64_t c = item >> 8, i = item & 0xFFu;
+    int32_t verdict = range_ok ? 0 : 1;
+    if (c >= g.S || i >= row) {
+      verdict = 3;
+    } else if (range_ok && bitmap != nullptr && bitmap[c * row + i] == 0) {
+      const uint8_t* r = bitmap + c * row;
+      const uint64_t j = i < g.k ? i % g.m : i - g.k;
+      uint32_t others = i < g.k ? r[g.k + j] == 0 : 0;
+      for (uint64_t l = j; l < g.k; l += g.m) others += l != i && r[l] == 0;
+      if (others != 0) verdict = 4;
+    }
+    if (verdict != 0) atomicMax(status, verdict);
+  }
+}
+
+// bytes[0, n) and tiles[0, n) into their exclusive prefixes in list order, in
+// place, the totals at [n]; *status raised to 1 if the byte total exceeds
+// out_bytes.  One workgroup walks the list in passes of 256 entries: a wave
+// scan by lane shifts, the four wave totals through LDS, and the running sums
+// carried from pass to pass -- integer sums, so exact and the same whatever
+// the launch.  The tile counts cannot overflow 32 bits (xec_readv_device's
+// host check over n * ceil(bs / 1024)).  n / 256 dependent passes of one load,
+// one scan and one store: at n = 2^20 (4,096 passes) the check and this scan
+// together took at most 3.2 ms of a 4.0 ms xec_readv_device call whose read
+// kernel ran 0.75 ms (16-byte entries, tools/readv_bench.py --scan), under
+// 0.8 us a pass; at the 1,024 entries of a request queue it is four passes.
+__global__ __launch_bounds__(256) void readv_scan_kernel(uint64_t* bytes, uint32_t* tiles,
+                                                        uint64_t n, uint64_t out_bytes,
+                                                        int32_t* status) {
+  __shared__ unsigned long long wave_bytes[4];
+  __shared__ uint32_t wave_tiles[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  unsigned long long carry_bytes = 0;
+  uint32_t carry_tiles = 0;
+  for (uint64_t base = 0; base < n; base += 256) {
+    const uint64_t e = base + threadIdx.x;
+    const unsigned long long b = e < n ? bytes[e] : 0;
+    const uint32_t q = e < n ? tiles[e] : 0;
+    unsigned long long sb = b;  // inclusive over the wave
+    uint32_t sq = q;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+      const unsigned long long ub = __shfl_up(sb, d, 64);
+      const uint32_t uq = __shfl_up(sq, d, 64);
+      if (lane >= d) {
+        sb += ub;
+        sq += uq;
+      }
+    }
+    if (lane == 63) {
+      wave_bytes[wave] = sb;
+      wave_tiles[wave] = sq;
+    }
+    __syncthreads();
+    unsigned long long before_bytes = carry_bytes;
+    uint32_t before_tiles = carry_tiles;
+    for (uint32_t v = 0; v < 4; ++v) {
+      if (v < wave) {
+        before_bytes += wave_bytes[v];
+        before_tiles += wave_tiles[v];
+      }
+      carry_bytes += wave_bytes[v];
+      carry_tiles += wave_tiles[v];
+    }
+    if (e < n) {
+      bytes[e] = before_bytes + sb - b;
+      tiles[e] = before_tiles + sq - q;
+    }
+    __syncthreads();  // the wave totals are free for the next pass
+  }
+  if (threadIdx.x == 0) {
+    bytes[n] = carry_bytes;
+    tiles[n] = carry_tiles;
+    if (carry_bytes > out_bytes) atomicMax(status, 1 /* XEC_INVALID_SIZE */);
+  }
+}
+
+hipError_t launch_readv(const void* d_data, const void* d_parity, void* d_out, const Geometry& g,
+                        const LaunchShape& ls, int tiling, uint64_t n, uint64_t tiles,
+                        const uint32_t* d_table, const uint32_t* h_table, hipStream_t s,
+                        const uint8_t* d_bitmap, const uint32_t* d_work) {
+  if (n == 0) return hipSuccess;
+  if (d_out == nullptr || n > 0xFFFFFFFFull || tiles > 0xFFFFFFFFull || g.k + g.m > 256 ||
+      tiling < kReadListTiles || tiling > kReadDevTiles)
+    return hipErrorInvalidValue;
+  if (tiling == kReadArgListTiles ? (n > kReadvArgEntries || h_table == nullptr)
+                                  : d_table == nullptr)
+    return hipErrorInvalidValue;
+  if (tiling == kReadDevTiles && (g.gate == nullptr || d_work == nullptr))
+    return hipErrorInvalidValue;
+  const uint8_t* d = static_cast<const uint8_t*>(d_data);
+  const uint8_t* p = static_cast<const uint8_t*>(d_parity);
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  const uint32_t grid = grid_for(tiles, ls.max_grid, ls.threads);
+  const uint32_t lds = ls.lds_bytes;
+  const uint32_t n32 = (uint32_t)n;
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    switch (tiling) {
+      case kReadArgListTiles:
+        return with_readv_capacity(n, [&](auto cap) {
+          constexpr uint32_t CAP = decltype(cap)::value;  // h_table is laid out for cap = CAP
+          return launch_codec(readv_arglist_kernel<NM, U, NT, T, CAP>, grid, T, lds, s, d, p, out,
+                              n32, g,
+                              arg_items<xec_readv_table_words(CAP)>(h_table, xec_readv_table_words(CAP)));
+        });
+      case kReadListTiles:
+        return launch_codec(readv_list_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_table,
+                            n32, g);
+      default:
+        return launch_codec(readv_dev_kernel<NM, U, NT, T>, grid, T, lds, s, d, p, out, d_table,
+                            d_bitmap, d_work, n32, g);
+    }
+  });
+}
+
+hipError_t launch_readv_check(const uint8_t* d_bitmap, const uint32_t* d_iov, uint64_t n,
+                              const Geometry& g, uint64_t tile_bytes, uint32_t* d_work,
+                              int32_t* d_status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  return launch(readv_check_kernel, grid_for((n + 255) / 256, 8192, 256), 256, 0, s, d_bitmap,
+                d_iov, n, g, tile_bytes, reinterpret_cast<uint64_t*>(d_work),
+                d_work + 2 * (n + 1), d_status);
+}
+
+hipError_t launch_readv_scan(uint32_t* d_work, uint64_t n, uint64_t out_bytes, int32_t* d_status,
+                             hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  return launch(readv_scan_kernel, 1, 256, 0, s, reinterpret_cast<uint64_t*>(d_work),
+                d_work + 2 * (n + 1), n, out_bytes, d_status);
 }
 
 // ---------------------------------------------------------------------------

@@ -434,6 +434,81 @@ extern "C" xec_status xec_check_read_items(const uint8_t* bm, size_t S, size_t k
   return xec_scan_read_items(bm, S, k, m, items, n_items, nullptr, n_lost);
 }
 
+// ---- vectored read plan (xec_readv, xec_check_readv) ----------------------------
+// The read scan's rule per entry, each with its own range, and the table of
+// xec_internal.h.  One walk: a broken range anywhere outranks an entry out of
+// range, which outranks an unservable one, so nothing stops the walk early; an
+// entry is looked up in the bitmap only when its c and i are in range.
+xec_status xec_plan_readv(const uint8_t* bm, size_t S, size_t bs, size_t k, size_t m,
+                          const xec_iov* iov, size_t n, size_t tile_bytes, size_t cap,
+                          uint32_t* table, XecReadvPlan* plan) {
+  XecReadvPlan local;
+  XecReadvPlan& p = plan != nullptr ? *plan : local;
+  p = XecReadvPlan{};
+  if (k < 1 || m < 1 || k % m != 0 || (iov == nullptr && n != 0))
+    return p.range_status = p.items_status = XEC_INVALID_COUNTS;
+  if (table != nullptr)
+    for (size_t w = 0; w < xec_readv_table_words(cap); ++w) table[w] = 0;
+  uint32_t* col = table != nullptr ? table + cap + 1 : nullptr;  // item, offset, len, out lo, hi
+  uint32_t* bits = table != nullptr ? table + 6 * cap + 1 : nullptr;
+  const size_t row = k + m;
+  bool bad_range = false, bad_item = false, unservable = false;
+  uint64_t bytes = 0, tiles = 0;
+  size_t lost = 0;
+  for (size_t t = 0; t < n; ++t) {
+    const uint64_t offset = iov[t].offset, len = iov[t].len;
+    if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset + len > bs) bad_range = true;
+    if (table != nullptr) {
+      table[t] = static_cast<uint32_t>(tiles);
+      col[t] = iov[t].item;
+      col[cap + t] = iov[t].offset;
+      col[2 * cap + t] = iov[t].len;
+      col[3 * cap + t] = static_cast<uint32_t>(bytes);
+      col[4 * cap + t] = static_cast<uint32_t>(bytes >> 32);
+    }
+    bytes += len;
+    tiles += (len + tile_bytes - 1) / tile_bytes;
+    const size_t c = iov[t].item >> 8, i = iov[t].item & 0xFFu;
+    if (c >= S || i >= row) {
+      bad_item = true;
+      continue;
+    }
+    if (bm == nullptr) continue;
+    const uint8_t* r = bm + c * row;
+    if (r[i] != 0) continue;
+    const size_t j = i < k ? i % m : i - k;
+    bool alone = i >= k || r[k + j] != 0;
+    for (size_t l = j; l < k && alone; l += m) alone = l == i || r[l] != 0;
+    if (!alone) {
+      unservable = true;
+      continue;
+    }
+    ++lost;
+    if (bits != nullptr) bits[t >> 5] |= 1u << (t & 31);
+  }
+  if (table != nullptr) table[n] = static_cast<uint32_t>(tiles);
+  p.total_bytes = bytes;
+  p.total_tiles = tiles;
+  if (bad_range) return p.range_status = p.items_status = XEC_INVALID_SIZE;
+  if (bad_item) return p.items_status = XEC_INVALID_COUNTS;
+  if (unservable) return p.items_status = XEC_DECODE_FAILURE;
+  p.n_lost = lost;
+  return XEC_SUCCESS;
+}
+
+extern "C" xec_status xec_check_readv(const uint8_t* bm, size_t S, size_t bs, size_t k, size_t m,
+                                      const xec_iov* iov, size_t n_items, size_t* n_lost,
+                                      size_t* total_bytes) {
+  if (n_lost) *n_lost = 0;
+  if (total_bytes) *total_bytes = 0;
+  XecReadvPlan plan;
+  const xec_status st = xec_plan_readv(bm, S, bs, k, m, iov, n_items, 1024, 0, nullptr, &plan);
+  if (st != XEC_SUCCESS) return st;
+  if (n_lost) *n_lost = plan.n_lost;
+  if (total_bytes) *total_bytes = plan.total_bytes;
+  return XEC_SUCCESS;
+}
+
 // ---- write scan (xec_write, xec_check_write_items) ------------------------------
 // The read scan's rule over written items (data blocks only, strictly
 // ascending), with two bits out per item.  A broken item rule anywhere in the

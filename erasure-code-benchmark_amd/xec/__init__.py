@@ -11,6 +11,8 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     device_list_bytes, digest, digest_host, encode, erase,
                     fill_splitmix64, init, locate, locate_work_bytes, repair, repair_device, repair_tiling_used,
                     check_read_items, read, read_device, read_scratch_bytes, read_tiling_used,
+                    IOV, check_readv, readv, readv_device, readv_device_work_bytes,
+                    readv_scratch_bytes, readv_tiling_used,
                     select_lost_blocks, set_decode_tiling, set_kernel_events, set_launch,
                     set_occupancy,
                     set_rotation, set_validate_kernel,
@@ -29,7 +31,8 @@ __all__ = [
     "encode", "erase", "fill_splitmix64", "init", "locate", "locate_work_bytes", "repair",
     "repair_device",
     "repair_tiling_used", "check_read_items", "read", "read_device", "read_scratch_bytes",
-    "read_tiling_used", "select_lost_blocks", "set_decode_tiling",
+    "read_tiling_used", "IOV", "check_readv", "readv", "readv_device",
+    "readv_device_work_bytes", "readv_scratch_bytes", "readv_tiling_used", "select_lost_blocks", "set_decode_tiling",
     "set_kernel_events",
     "set_launch",
     "set_occupancy", "set_rotation", "set_validate_kernel", "status_string", "stripe_range",

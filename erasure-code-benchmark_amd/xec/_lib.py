@@ -35,6 +35,8 @@ EXPORTED = (
     "xec_digest_host", "xec_digest", "xec_locate", "xec_locate_work_bytes",
     "xec_read", "xec_read_scratch_bytes", "xec_read_device", "xec_check_read_items",
     "xec_read_tiling_used",
+    "xec_readv", "xec_readv_scratch_bytes", "xec_readv_device",
+    "xec_readv_device_work_bytes", "xec_check_readv", "xec_readv_tiling_used",
     "xec_update_range", "xec_update_range_device", "xec_digest_range_host",
     "xec_write", "xec_write_scratch_bytes", "xec_write_device", "xec_check_write_items",
     "xec_write_tiling_used",
@@ -133,6 +135,13 @@ def lib() -> ctypes.CDLL:
         "xec_read_device": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp], st),
         "xec_check_read_items": ([vp, sz, sz, sz, vp, sz, ctypes.POINTER(sz)], st),
         "xec_read_tiling_used": ([], ctypes.c_int),
+        "xec_readv": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, sz, vp], st),
+        "xec_readv_scratch_bytes": ([sz], sz),
+        "xec_readv_device": ([vp, vp, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, sz, vp, vp], st),
+        "xec_readv_device_work_bytes": ([sz], sz),
+        "xec_check_readv": ([vp, sz, sz, sz, sz, vp, sz, ctypes.POINTER(sz),
+                             ctypes.POINTER(sz)], st),
+        "xec_readv_tiling_used": ([], ctypes.c_int),
         "xec_update_range": ([vp, vp, vp, sz, sz, sz, sz, vp, sz, sz, sz, vp, vp, sz, vp], st),
         "xec_update_range_device": ([vp, vp, vp, sz, sz, sz, sz, vp, sz, sz, vp, vp], st),
         "xec_digest_range_host": ([vp, sz, sz], ctypes.c_uint64),

@@ -10,7 +10,12 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
+
 from ._lib import Status, lib
+
+#: xec_iov (include/xec.h): one entry of a vectored read, 12 bytes
+IOV = np.dtype([("item", "<u4"), ("offset", "<u4"), ("len", "<u4")])
 
 
 def _ptr(x) -> int:
@@ -319,6 +324,63 @@ def read_tiling_used() -> int:
     """xec_read_tiling_used: the tiling this thread's last read launched (0 none,
     3 list on the device, 4 list in the kernel arguments)."""
     return int(lib().xec_read_tiling_used())
+
+
+def readv(d_data, d_parity, S: int, bs: int, k: int, m: int, h_bitmap, h_iov, n_items: int,
+          d_out, out_bytes: int, d_scratch=None, scratch_bytes: int = 0, stream=None) -> Status:
+    """xec_readv -- xec_read with a range per entry: h_iov is a host array of
+    n_items IOV entries (item c << 8 | i, offset, len), and entry t's bytes go to
+    d_out + the sum of len over the entries before it (out_bytes = d_out's
+    capacity).  d_scratch (readv_scratch_bytes(n_items) device bytes) is needed
+    only past 256 entries."""
+    return Status(lib().xec_readv(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                  _ptr(h_bitmap) if h_bitmap is not None else None,
+                                  _ptr(h_iov) if h_iov is not None else None, n_items,
+                                  _ptr(d_out), out_bytes, _ptr(d_scratch), scratch_bytes,
+                                  _stream(stream)))
+
+
+def readv_device(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, d_iov,
+                 n_items: int, d_out, out_bytes: int, d_work, work_bytes: int, d_status,
+                 stream=None) -> Status:
+    """xec_readv_device -- the same with bitmap (None = all present) and entries on
+    the device, d_work of readv_device_work_bytes(n_items) device bytes; the
+    verdict lands in d_status (int32 device tensor: 0, 1 a bad range or an
+    output past out_bytes, 3 an entry out of range, 4 an entry not servable) in
+    stream order; capturable."""
+    return Status(lib().xec_readv_device(_ptr(d_data), _ptr(d_parity), S, bs, k, m,
+                                         _ptr(d_bitmap) if d_bitmap is not None else None,
+                                         _ptr(d_iov) if d_iov is not None else None, n_items,
+                                         _ptr(d_out), out_bytes, _ptr(d_work), work_bytes,
+                                         _ptr(d_status), _stream(stream)))
+
+
+def readv_scratch_bytes(n_items: int) -> int:
+    """xec_readv_scratch_bytes: 4 * (6 * n_items + 1 + ceil(n_items / 32)), 0 at 0."""
+    return int(lib().xec_readv_scratch_bytes(n_items))
+
+
+def readv_device_work_bytes(n_items: int) -> int:
+    """xec_readv_device_work_bytes: 12 * (n_items + 1) rounded up to 8, 0 at 0."""
+    return int(lib().xec_readv_device_work_bytes(n_items))
+
+
+def check_readv(h_bitmap, S: int, bs: int, k: int, m: int, h_iov,
+                n_items: int) -> tuple[Status, int, int]:
+    """xec_check_readv -- the host plan check xec_readv runs (no GPU, no init):
+    (status, entries that need a reconstruction, sum of len)."""
+    n_lost, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    st = Status(lib().xec_check_readv(_ptr(h_bitmap) if h_bitmap is not None else None,
+                                      S, bs, k, m,
+                                      _ptr(h_iov) if h_iov is not None else None, n_items,
+                                      ctypes.byref(n_lost), ctypes.byref(total)))
+    return st, int(n_lost.value), int(total.value)
+
+
+def readv_tiling_used() -> int:
+    """xec_readv_tiling_used: the tiling this thread's last readv launched (0 none,
+    3 table on the device, 4 table in the kernel arguments)."""
+    return int(lib().xec_readv_tiling_used())
 
 
 def erase(d_data, d_parity, S: int, bs: int, k: int, m: int, d_bitmap, stream=None) -> Status:

@@ -492,6 +492,124 @@ xec_status xec_check_read_items(const uint8_t* h_bitmap, size_t S, size_t k, siz
  * affected. */
 int xec_read_tiling_used(void);
 
+/* Vectored degraded read: xec_read with a range per entry, the shape of a
+ * store's read queue.  Everything xec_read says holds per entry, with the
+ * entry's own [offset, offset + len): a present block's range is copied, a
+ * lost block's range is reconstructed from the same range of the other k/m
+ * blocks of its class straight into d_out; data, parity and the bitmap are
+ * never written and the bytes a lost block holds are never read.  Entries may
+ * come in any order and may repeat; h_bitmap == NULL means everything is
+ * present; servability is xec_read's rule; the call is all-or-nothing over the
+ * requested entries.
+ * Output is packed in list order: entry t's bytes land at d_out + the sum of
+ * len over the entries before it.  These offsets are 64-bit, the total may
+ * pass 4 GiB.  out_bytes is the capacity of d_out; nothing past the total is
+ * written.
+ * When to use which (tools/readv_bench.py on one MI355X, 16+1 x 1 MiB x 256,
+ * 1,024 lost entries; DESIGN.md §3 *Vectored read*): when the ranges differ,
+ * one xec_readv replaces one xec_read per distinct range -- 1,024 entries over
+ * 64 ranges took 120 us from call to sync against 668 us for the 64 xec_read
+ * calls (44 against 613 us with every block present).  When every entry has
+ * the same range use xec_read: its tile needs no search and 1,024 items still
+ * travel in its kernel arguments, 7.9 us of kernel and 27 us from call to sync
+ * against xec_readv's 12.9 and 53 us.
+ * Checks, all on the host before anything is queued, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. xec_check_args;
+ *  3. n_items == 0 or S == 0 -> XEC_SUCCESS, nothing queued;
+ *  4. k + m > 256, S > 2^24 or bs >= 2^32 -> XEC_INVALID_SIZE;
+ *  5. d_out or h_iov NULL -> XEC_INVALID_SIZE;
+ *  6. d_out not 16-byte aligned -> XEC_INVALID_ALIGNMENT;
+ *  7. an entry with len == 0, offset % 16, len % 16 or offset + len > bs (in 64
+ *     bits) -> XEC_INVALID_SIZE;
+ *  8. sum len > out_bytes, a total number of tiles (below) that does not fit 32
+ *     bits, or d_out's sum len bytes overlapping the data or the parity range
+ *     -> XEC_INVALID_SIZE;
+ *  9. an entry with c >= S or i >= k + m -> XEC_INVALID_COUNTS;
+ * 10. an entry that is not servable -> XEC_DECODE_FAILURE;
+ * 11. more than 256 entries: d_scratch not 4-byte aligned ->
+ *     XEC_INVALID_ALIGNMENT; NULL or fewer than xec_readv_scratch_bytes(n_items)
+ *     bytes -> XEC_INVALID_SIZE.
+ * A rejected call queues nothing and writes nothing.  The kernel walks a table
+ * of six words per entry -- item, offset, len, the 64-bit output start and the
+ * entry's first tile, a tile being (entry, chunk of 16 * block_threads * unroll
+ * bytes of its range; 1 KiB at the default launch shape) -- plus one loss bit.
+ * Up to 256 entries travel in the kernel arguments (capacities 64 / 256; 1,024
+ * would ship 24 KiB with every launch) and d_scratch may be NULL.  A longer
+ * table is staged in the pinned memory the library keeps and uploaded on
+ * `stream` itself into d_scratch in one copy.  h_bitmap and h_iov are read
+ * before the call returns; the call is asynchronous on `stream`.  Not
+ * capturable, as xec_read: on a capturing stream a call with work returns
+ * XEC_DEVICE_ERROR with nothing queued.  Of xec_set_launch all four arguments
+ * apply, xec_set_rotation does not; xec_set_kernel_events times the read
+ * kernel. */
+typedef struct {
+  uint32_t item;   /* c << 8 | i, xec_read's packing: i in [0, k+m), i >= k = parity block i-k */
+  uint32_t offset; /* bytes into the block, multiple of 16 */
+  uint32_t len;    /* bytes, multiple of 16, > 0; offset + len <= bs */
+} xec_iov;         /* 12 bytes, 4-byte aligned */
+
+xec_status xec_readv(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                     size_t m, const uint8_t* h_bitmap, const xec_iov* h_iov, size_t n_items,
+                     void* d_out, size_t out_bytes, void* d_scratch, size_t scratch_bytes,
+                     hipStream_t stream);
+
+/* Scratch bytes xec_readv needs for a table of n_items entries:
+ * 4 * (6 * n_items + 1 + ceil(n_items / 32)), 0 for n_items == 0.  Needed only
+ * past 256 entries. */
+size_t xec_readv_scratch_bytes(size_t n_items);
+
+/* Device-resident form of xec_readv: bitmap and entries in device memory, no
+ * host work and no limit on n_items, so it can be captured in a hipGraph; a
+ * replay serves whatever d_iov and d_bitmap hold at replay time, lengths
+ * included.  d_bitmap == NULL: everything present.
+ * Host checks, before anything is queued, in this order: XEC_NOT_INITIALIZED;
+ * xec_check_args; d_status NULL or not 4-byte aligned -> XEC_INVALID_ALIGNMENT;
+ * n_items == 0 or S == 0 -> XEC_SUCCESS with only *d_status = 0 queued; step 4
+ * of xec_readv; d_out, d_iov or d_work NULL -> XEC_INVALID_SIZE; work_bytes <
+ * xec_readv_device_work_bytes(n_items) -> XEC_INVALID_SIZE; d_out not 16-byte,
+ * d_iov not 4-byte or d_work not 8-byte aligned -> XEC_INVALID_ALIGNMENT;
+ * d_out's out_bytes overlapping data or parity -> XEC_INVALID_SIZE;
+ * n_items * ceil(bs / 1024) >= 2^32 -> XEC_INVALID_SIZE (a 32-bit tile count
+ * cannot overflow at any launch shape).
+ * Enqueues on `stream`: *d_status = 0 (a memset, as xec_read_device); a check
+ * kernel, one thread per entry, that leaves *d_status at the MAXIMUM over the
+ * entries of 0 (servable), 1 (a range that breaks step 7 of xec_readv), 3
+ * (c >= S or i >= k + m) and 4 (in range but not servable) -- an entry with a
+ * nonzero verdict is never dereferenced beyond its own 12 bytes -- and writes
+ * each entry's tile count and length into d_work; a scan kernel that turns
+ * those into exclusive prefixes in list order and raises *d_status to 1 if
+ * the byte total exceeds out_bytes; then the read kernel, which does nothing
+ * if *d_status != 0 and otherwise delivers the bytes xec_readv delivers.  Its
+ * grid is fixed at launch from the bound the host knows, out_bytes / tile
+ * bytes + n_items possible tiles, clamped as xec_decode_device_list clamps its
+ * grid (xec_set_launch's max_grid overrides it). */
+xec_status xec_readv_device(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
+                            size_t m, const uint8_t* d_bitmap, const xec_iov* d_iov,
+                            size_t n_items, void* d_out, size_t out_bytes, void* d_work,
+                            size_t work_bytes, int32_t* d_status, hipStream_t stream);
+
+/* Work bytes xec_readv_device needs: 12 * (n_items + 1) rounded up to a
+ * multiple of 8 (a 64-bit output start and a 32-bit tile start per entry, and
+ * the totals), 0 for n_items == 0. */
+size_t xec_readv_device_work_bytes(size_t n_items);
+
+/* Host-only plan check xec_readv runs over its entries (no GPU and no xec_init
+ * needed): steps 7, 9 and 10 of xec_readv in that order.  k, m invalid as in
+ * xec_check_args, or h_iov NULL with n_items > 0 -> XEC_INVALID_COUNTS, as
+ * xec_check_read_items.  On success *n_lost (may be NULL) = the entries that
+ * need a reconstruction, a repeat counted each time, and *total_bytes (may be
+ * NULL) = sum len. */
+xec_status xec_check_readv(const uint8_t* h_bitmap, size_t S, size_t bs, size_t k, size_t m,
+                           const xec_iov* h_iov, size_t n_items, size_t* n_lost,
+                           size_t* total_bytes);
+
+/* Diagnostics: which tiling the calling thread's most recent xec_readv or
+ * xec_readv_device launched -- 0 none (an error, or nothing to read),
+ * XEC_TILING_ARG_LIST or XEC_TILING_LIST (xec_readv), XEC_TILING_LIST
+ * (xec_readv_device).  The other *_tiling_used values are not affected. */
+int xec_readv_tiling_used(void);
+
 /* Ranged update with digest upkeep (no reference counterpart): xec_update
  * over bytes [offset, offset + len) of each named block only, following
  * xec_read's range rules.  For every named block i of stripe c,
@@ -784,7 +902,7 @@ xec_status xec_set_launch(int unroll, int max_grid, int cache_policy, int block_
  * none at 1 and 2.  The repair kernels take the same table;
  * xec_verify too, except 1 at k/m = 8 (its own sweep); the update kernels, the
  * write kernels and the digest kernel run uncapped at every k/m (their own sweeps); the read
- * kernel takes the table, except that an xec_read whose items are all present
+ * kernel takes the table, except that an xec_read or xec_readv whose items are all present
  * runs uncapped.  The reserved LDS keeps other kernels' LDS
  * users off those CUs while a launch runs.  Returns XEC_INVALID_SIZE outside
  * 0..8. */
@@ -827,7 +945,7 @@ xec_status xec_set_validate_kernel(int mode);
  * so results are identical; it changes which columns of the stripes in flight
  * together are read at once.  0 = automatic (the measured default), -1 = none,
  * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
- * It does not apply to xec_read / xec_read_device, xec_update_range /
+ * It does not apply to xec_read / xec_read_device, xec_readv / xec_readv_device, xec_update_range /
  * xec_update_range_device and xec_write / xec_write_device: their tiles walk the chunks of each item's byte
  * range, not a column of every stripe. */
 xec_status xec_set_rotation(int tiles);
@@ -870,7 +988,7 @@ int xec_decode_arg_capacity_used(void);
 /* Diagnostics / measurement: the calling thread's NEXT xec_encode, xec_decode,
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
- * xec_digest, xec_locate, xec_read, xec_read_device, xec_update_range,
+ * xec_digest, xec_locate, xec_read, xec_read_device, xec_readv, xec_readv_device, xec_update_range,
  * xec_update_range_device, xec_write or xec_write_device call
  * launches its encode / decode / repair / verify / update / digest / read / write kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
