@@ -1234,6 +1234,146 @@ xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t
   return XEC_SUCCESS;
 }
 
+// ---- shard-major layout ------------------------------------------------------
+// xec_encode_shards / xec_repair_shards_device / xec_verify_shards: encode, the
+// class-tile repair and the scrub over one buffer per shard (include/xec.h).
+// The table is read on the host before the call returns and travels in the
+// kernel arguments, so there is no host work a capture would miss.  Residency:
+// auto_occupancy / verify_auto_occupancy, tables swept on the batch layout and
+// NOT swept on this one (tools/shards_bench.py compares the two layouts at the
+// tables' values only).
+static thread_local int g_shards_cap_used = 0;  // xec_shards_arg_capacity_used
+
+// [p, p + (S-1)*stride + bs) of one shard; the caller made sure it is representable.
+struct ShardHull {
+  uintptr_t lo, hi;
+  size_t stride;
+};
+
+// Steps 3 to 7 of xec_check_shards, S > 0.
+static xec_status check_shard_table(const void* const* h_shards, size_t data_stride,
+                                    size_t parity_stride, size_t S, size_t bs, size_t k,
+                                    size_t m) {
+  if (k > xec::kShardPtrs || m > xec::kShardPtrs - k) return XEC_INVALID_SIZE;
+  const size_t n = k + m;
+  if (h_shards == nullptr) return XEC_INVALID_SIZE;
+  for (size_t i = 0; i < n; ++i)
+    if (h_shards[i] == nullptr) return XEC_INVALID_SIZE;
+  for (size_t i = 0; i < n; ++i)
+    if (reinterpret_cast<uintptr_t>(h_shards[i]) % kAlign != 0) return XEC_INVALID_ALIGNMENT;
+  if (data_stride % kAlign != 0 || parity_stride % kAlign != 0) return XEC_INVALID_ALIGNMENT;
+  if (data_stride < bs || parity_stride < bs) return XEC_INVALID_SIZE;
+  const size_t big = data_stride > parity_stride ? data_stride : parity_stride;
+  if (S - 1 > (SIZE_MAX - bs) / big) return XEC_INVALID_SIZE;  // (S-1)*stride + bs in 64 bits
+  ShardHull hull[xec::kShardPtrs];
+  for (size_t i = 0; i < n; ++i) {
+    const size_t stride = i < k ? data_stride : parity_stride;
+    const size_t len = (S - 1) * stride + bs;
+    const uintptr_t p = reinterpret_cast<uintptr_t>(h_shards[i]);
+    if (len > UINTPTR_MAX - p) return XEC_INVALID_SIZE;  // the hull itself must not wrap
+    hull[i] = ShardHull{p, p + len, stride};
+  }
+  for (size_t x = 0; x < n; ++x)
+    for (size_t y = x + 1; y < n; ++y) {
+      const ShardHull &a = hull[x], &b = hull[y];
+      if (a.hi <= b.lo || b.hi <= a.lo) continue;  // disjoint hulls
+      if (a.stride != b.stride) return XEC_INVALID_SIZE;
+      // interleaved: the blocks of y sit at a fixed offset d inside x's stride
+      const size_t s = a.stride;
+      const size_t d = b.lo >= a.lo ? (b.lo - a.lo) % s : (s - (a.lo - b.lo) % s) % s;
+      if (d < bs || s - d < bs) return XEC_INVALID_SIZE;
+    }
+  return XEC_SUCCESS;
+}
+
+xec_status xec_check_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                            size_t S, size_t bs, size_t k, size_t m) {
+  const xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  return check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+}
+
+int xec_shards_arg_capacity_used(void) { return g_shards_cap_used; }
+
+xec_status xec_encode_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  const xec_status st = xec_check_shards(h_shards, data_stride, parity_stride, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  const xec::LaunchShape ls = launch_shape(bs, auto_occupancy(k / m));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_encode_shards(h_shards, data_stride, parity_stride, g, ls, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
+xec_status xec_repair_shards_device(const void* const* h_shards, size_t data_stride,
+                                    size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                    const uint8_t* d_bitmap, int32_t* d_status,
+                                    hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (d_bitmap == nullptr && S != 0) return XEC_INVALID_SIZE;
+  if (S != 0) {
+    st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+    if (st != XEC_SUCCESS) return st;
+  }
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  const xec::LaunchShape ls = launch_shape(bs, auto_occupancy(k / m));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_check(d_bitmap, g, d_status, stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  if (xec::launch_repair_shards(h_shards, data_stride, parity_stride, d_bitmap, g, ls, stream) !=
+      hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
+xec_status xec_verify_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, uint8_t* d_flags,
+                             uint32_t* d_count, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (reinterpret_cast<uintptr_t>(d_count) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+  if (d_flags == nullptr && S != 0) return XEC_INVALID_SIZE;
+  if (S != 0) {
+    st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+    if (st != XEC_SUCCESS) return st;
+  }
+  if (d_count != nullptr &&
+      hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  if (hipMemsetAsync(d_flags, 0, S * m, stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  const xec::LaunchShape ls = launch_shape(bs, verify_auto_occupancy(k / m));
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_verify_shards(h_shards, data_stride, parity_stride, d_flags, g, ls, stream) !=
+      hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  if (d_count != nullptr &&
+      xec::launch_count_flags(d_flags, S * m, d_count, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  return XEC_SUCCESS;
+}
+
 // ---- in-place block update -----------------------------------------------------
 // xec_update / xec_update_device: parity[c][i % m] ^= data[c][i] ^ new, then
 // data[c][i] = new, for the named blocks only (xec_kernels.hip, update).  The

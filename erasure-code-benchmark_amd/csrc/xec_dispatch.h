@@ -79,4 +79,15 @@ auto with_readv_capacity(uint64_t n, F&& f) {
   return f(std::integral_constant<uint32_t, 256>{});
 }
 
+// A shard table (xec_encode_shards and its siblings) is k + m 64-bit pointers by
+// value in the kernel arguments: two capacities, 64 pointers (512 B) and 256
+// (2 KiB), which is also the most shards a call takes.
+inline uint32_t shard_tab_capacity(uint64_t n) { return n <= 64 ? 64 : 256; }
+
+template <class F>
+auto with_shard_capacity(uint64_t n, F&& f) {
+  if (shard_tab_capacity(n) == 64) return f(std::integral_constant<uint32_t, 64>{});
+  return f(std::integral_constant<uint32_t, 256>{});
+}
+
 }  // namespace xec

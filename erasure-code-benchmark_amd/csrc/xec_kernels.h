@@ -111,7 +111,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
 }
 
 // The codec kernels (encode, every decode, repair and update tiling, verify,
-// digest, read, ranged update, degraded write) go through this: as launch(), but with the thread's pending kernel events,
+// digest, read, ranged update, degraded write, the shard-layout three) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -336,6 +336,30 @@ hipError_t launch_write(void* d_data, void* d_parity, const void* d_new, const v
 // stream-ordered; d_bitmap == nullptr launches nothing.
 hipError_t launch_write_check(const uint8_t* d_bitmap, const uint8_t* d_mask, const Geometry& g,
                               int32_t* d_status, hipStream_t s);
+// Shard-major layout (xec_encode_shards, xec_repair_shards_device,
+// xec_verify_shards): encode, the class-tile repair and the scrub over one
+// buffer per shard instead of the batch layout.  h_shards = k + m device
+// pointers in host memory, the k data shards then the m parity shards, read at
+// launch and passed by value in the kernel arguments (ShardTab, capacity 64 or
+// 256 by shard_tab_capacity, xec_dispatch.h; k + m <= kShardPtrs): nothing is
+// copied.  Data block i of stripe c is at h_shards[i] + c*dstride, parity block
+// j at h_shards[k + j] + c*pstride; the caller checked alignment, strides and
+// overlap (xec_check_shards).  Tiles, g and ls as launch_encode / launch_repair
+// with kRepairClassTiles (g.gate must be set; d_bitmap = the batch bitmap) /
+// launch_verify (the caller zeroes d_flags first).
+constexpr uint64_t kShardPtrs = 256;  // the largest capacity
+template <uint32_t N>
+struct ShardTab {
+  uint8_t* v[N];
+};
+hipError_t launch_encode_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const Geometry& g, const LaunchShape& ls, hipStream_t s);
+hipError_t launch_repair_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const uint8_t* d_bitmap, const Geometry& g, const LaunchShape& ls,
+                                hipStream_t s);
+hipError_t launch_verify_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                uint8_t* d_flags, const Geometry& g, const LaunchShape& ls,
+                                hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

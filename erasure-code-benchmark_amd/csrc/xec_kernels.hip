@@ -2576,6 +2576,256 @@ hipError_t launch_write_check(const uint8_t* d_bitmap, const uint8_t* d_mask, co
                 d_mask, g, d_status);
 }
 
+// ---------------------------------------------------------------------------
+// Shard-major layout (xec_encode_shards, xec_repair_shards_device,
+// xec_verify_shards): the layout-aware siblings of encode_kernel,
+// repair_class_kernel and verify_kernel.  The class tile, its walk from the end
+// of the batch, the column rotation, the fast path and the store policies are
+// theirs; what differs is where a block lives.  The k + m shard base pointers
+// travel by value in the kernel arguments (ShardTab<CAP>, xec_kernels.h), so
+//   member r of class j, stripe c : tab.v[j + r*m] + c*dstride
+//   parity block j of stripe c    : tab.v[k + j]   + c*pstride
+// -- each a scalar load from the argument segment at a wave-uniform index plus
+// a wave-uniform stripe offset; only the lane's byte offset is per lane.  The
+// index is below k + m <= CAP for every tile (the launcher checks it).  No
+// LDS, no atomics, and the older kernels and their helpers above are
+// untouched: these are emitted after them.
+// ---------------------------------------------------------------------------
+
+// xor_members over a shard table: member r is tab.v[first + r*m] + doff, except
+// member `subst`, whose bytes come from `sub` (the class's parity block).
+template <int NM, int U, bool NT, int T, int SAUX, uint32_t CAP>
+__device__ __forceinline__ void xor_shard_members(const ShardTab<CAP>& tab, uint64_t first,
+                                                  uint64_t m, uint64_t doff, const uint8_t* sub,
+                                                  int subst, uint8_t* dst, uint64_t off,
+                                                  uint64_t bs, uint32_t nm_rt) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  if constexpr (NM > 0) {
+    const bool whole = off + (U - 1) * kStep < bs;  // the tile's last granule row is inside
+    if (whole) {
+      u32x4 v[NM][U];
+#pragma unroll
+      for (int r = 0; r < NM; ++r) {
+        const uint8_t* src = (r == subst ? sub : tab.v[first + (uint64_t)r * m] + doff) + off;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = ld16<NT>(src + u * kStep);
+      }
+      if constexpr (NM >= 32) __builtin_amdgcn_sched_barrier(0);  // as xor_members
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u32x4 acc = v[0][u];
+#pragma unroll
+        for (int r = 1; r < NM; ++r) acc ^= v[r][u];
+        st16_block<NT, SAUX>(dst, off + u * kStep, acc);
+      }
+      return;
+    }
+  }
+  // Ragged tail of a block, or a member count without a compiled unroll.
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : nm_rt;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t o = off + u * kStep;
+    if (o >= bs) continue;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    uint32_t r = 0;
+    for (; r + 8 <= nm; r += 8) {
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int rr = (int)(r + q);
+        v[q] = ld16<NT>((rr == subst ? sub : tab.v[first + (uint64_t)rr * m] + doff) + o);
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc ^= v[q];
+    }
+    for (; r < nm; ++r)
+      acc ^= ld16<NT>(((int)r == subst ? sub : tab.v[first + (uint64_t)r * m] + doff) + o);
+    st16_block<NT, SAUX>(dst, o, acc);
+  }
+}
+
+// reduce_members over a shard table: the class's members and its parity block
+// at `extra`, nothing stored.
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__device__ __forceinline__ u32x4 reduce_shard_members(const ShardTab<CAP>& tab, uint64_t first,
+                                                      uint64_t m, uint64_t doff,
+                                                      const uint8_t* extra, uint64_t off,
+                                                      uint64_t bs, uint32_t nm_rt) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  u32x4 any = {0u, 0u, 0u, 0u};
+  if constexpr (NM > 0) {
+    const bool whole = off + (U - 1) * kStep < bs;
+    if (whole) {
+      u32x4 v[NM + 1][U];
+#pragma unroll
+      for (int r = 0; r < NM; ++r) {
+        const uint8_t* src = tab.v[first + (uint64_t)r * m] + doff + off;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = ld16<NT>(src + u * kStep);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[NM][u] = ld16<NT>(extra + off + u * kStep);
+      if constexpr (NM >= 32) __builtin_amdgcn_sched_barrier(0);  // as xor_members
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u32x4 acc = v[0][u];
+#pragma unroll
+        for (int r = 1; r <= NM; ++r) acc ^= v[r][u];
+        any |= acc;
+      }
+      return any;
+    }
+  }
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : nm_rt;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t o = off + u * kStep;
+    if (o >= bs) continue;
+    u32x4 acc = ld16<NT>(extra + o);
+    uint32_t r = 0;
+    for (; r + 8 <= nm; r += 8) {
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = ld16<NT>(tab.v[first + (uint64_t)(r + q) * m] + doff + o);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc ^= v[q];
+    }
+    for (; r < nm; ++r) acc ^= ld16<NT>(tab.v[first + (uint64_t)r * m] + doff + o);
+    any |= acc;
+  }
+  return any;
+}
+
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void encode_shards_kernel(Geometry g, uint64_t dstride,
+                                                          uint64_t pstride, ShardTab<CAP> tab) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as encode
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    xor_shard_members<NM, U, NT, T, kEncodeStoreAux>(tab, tc.j, g.m, tc.c * dstride, nullptr, -1,
+                                                     tab.v[g.k + tc.j] + tc.c * pstride, off, g.bs,
+                                                     (uint32_t)g.nm);
+  }
+}
+
+// Gated on the check's verdict and reading its class's bitmap bytes as
+// repair_class_kernel does: a lost parity block is encode's reduction (stored
+// nt), a lost member decode's with the parity block in its place (stored sc1).
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void repair_shards_kernel(const uint8_t* __restrict__ bitmap,
+                                                          Geometry g, uint64_t dstride,
+                                                          uint64_t pstride, ShardTab<CAP> tab) {
+  if (g.gate != nullptr && *(const_i32_as4)g.gate != 0) return;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t row = reinterpret_cast<uint64_t>(bitmap + tc.c * (g.k + g.m));
+    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    uint8_t* par = tab.v[g.k + tc.j] + tc.c * pstride;
+    if (sbyte(row + g.k + tc.j) == 0) {
+      xor_shard_members<NM, U, NT, T, kEncodeStoreAux>(tab, tc.j, g.m, tc.c * dstride, nullptr, -1,
+                                                       par, off, g.bs, nm);
+      continue;
+    }
+    uint32_t lost = nm;
+    for (uint32_t r = 0; r < nm; ++r)
+      if (sbyte(row + tc.j + (uint64_t)r * g.m) == 0) { lost = r; break; }
+    if (lost == nm) continue;
+    xor_shard_members<NM, U, NT, T, kDecodeStoreAux>(
+        tab, tc.j, g.m, tc.c * dstride, par, (int)lost,
+        tab.v[tc.j + (uint64_t)lost * g.m] + tc.c * dstride, off, g.bs, nm);
+  }
+}
+
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void verify_shards_kernel(uint8_t* __restrict__ flags, Geometry g,
+                                                          uint64_t dstride, uint64_t pstride,
+                                                          ShardTab<CAP> tab) {
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    const TileCoord tc = tile_coord(t, g);
+    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    const u32x4 v = reduce_shard_members<NM, U, NT, T>(tab, tc.j, g.m, tc.c * dstride,
+                                                       tab.v[g.k + tc.j] + tc.c * pstride, off,
+                                                       g.bs, (uint32_t)g.nm);
+    // every lane of the workgroup gets here: the tile loop is uniform
+    const uint64_t bad = __ballot((v.x | v.y | v.z | v.w) != 0u);
+    if (bad != 0 && (threadIdx.x & 63u) == 0) flags[tc.c * g.m + tc.j] = 1;
+  }
+}
+
+namespace {
+
+// The k + m of h_shards in a ShardTab<CAP>, the rest null (never indexed).
+template <uint32_t CAP>
+ShardTab<CAP> shard_tab(const void* const* h_shards, uint64_t n) {
+  ShardTab<CAP> t;
+  for (uint64_t i = 0; i < CAP; ++i)
+    t.v[i] = i < n ? static_cast<uint8_t*>(const_cast<void*>(h_shards[i])) : nullptr;
+  return t;
+}
+
+// with_shape and with_shard_capacity (xec_dispatch.h) in one: f(shape, capacity).
+template <class F>
+hipError_t with_shard_shape(const Geometry& g, const LaunchShape& ls, F&& f) {
+  return with_shape(g.nm, ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    return with_shard_capacity(g.k + g.m, [&](auto cap) { return f(sh, cap); });
+  });
+}
+
+bool shard_launch_ok(const void* const* h_shards, const Geometry& g) {
+  return h_shards != nullptr && g.k + g.m <= kShardPtrs;
+}
+
+}  // namespace
+
+hipError_t launch_encode_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const Geometry& g, const LaunchShape& ls, hipStream_t s) {
+  if (g.total_tiles == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g)) return hipErrorInvalidValue;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_shard_shape(g, ls, [&](auto sh, auto cap) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch_codec(encode_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s, g,
+                        dstride, pstride, shard_tab<CAP>(h_shards, g.k + g.m));
+  });
+}
+
+hipError_t launch_repair_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const uint8_t* d_bitmap, const Geometry& g, const LaunchShape& ls,
+                                hipStream_t s) {
+  if (g.total_tiles == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g) || g.gate == nullptr) return hipErrorInvalidValue;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_shard_shape(g, ls, [&](auto sh, auto cap) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch_codec(repair_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s,
+                        d_bitmap, g, dstride, pstride, shard_tab<CAP>(h_shards, g.k + g.m));
+  });
+}
+
+hipError_t launch_verify_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                uint8_t* d_flags, const Geometry& g, const LaunchShape& ls,
+                                hipStream_t s) {
+  if (g.total_tiles == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g)) return hipErrorInvalidValue;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_shard_shape(g, ls, [&](auto sh, auto cap) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch_codec(verify_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s,
+                        d_flags, g, dstride, pstride, shard_tab<CAP>(h_shards, g.k + g.m));
+  });
+}
+
 // Test hook only (tests/host/error_preserve.cpp).  A user who finds it set
 // is told once, on stderr, that every launch of the library will fail
 // (a silent hook in the shipped library).

@@ -20,7 +20,9 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     update_tiling_used, validate_blocks, verify, write_validation_pattern,
                     digest_range_host, update_range, update_range_device,
                     check_write_items, write, write_device, write_scratch_bytes,
-                    write_tiling_used)
+                    write_tiling_used,
+                    check_shards, encode_shards, repair_shards_device, shard_table,
+                    shards_arg_capacity_used, verify_shards)
 from .partition import stripe_range
 
 __all__ = [
@@ -40,4 +42,6 @@ __all__ = [
     "verify", "write_validation_pattern",
     "digest_range_host", "update_range", "update_range_device",
     "check_write_items", "write", "write_device", "write_scratch_bytes", "write_tiling_used",
+    "check_shards", "encode_shards", "repair_shards_device", "shard_table",
+    "shards_arg_capacity_used", "verify_shards",
 ]

@@ -40,6 +40,8 @@ EXPORTED = (
     "xec_update_range", "xec_update_range_device", "xec_digest_range_host",
     "xec_write", "xec_write_scratch_bytes", "xec_write_device", "xec_check_write_items",
     "xec_write_tiling_used",
+    "xec_check_shards", "xec_encode_shards", "xec_repair_shards_device", "xec_verify_shards",
+    "xec_shards_arg_capacity_used",
 )
 
 
@@ -151,6 +153,11 @@ def lib() -> ctypes.CDLL:
         "xec_check_write_items": ([vp, sz, sz, sz, vp, sz, ctypes.POINTER(sz),
                                    ctypes.POINTER(sz)], st),
         "xec_write_tiling_used": ([], ctypes.c_int),
+        "xec_check_shards": ([vp, sz, sz, sz, sz, sz, sz], st),
+        "xec_encode_shards": ([vp, sz, sz, sz, sz, sz, sz, vp], st),
+        "xec_repair_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_verify_shards": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_shards_arg_capacity_used": ([], ctypes.c_int),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

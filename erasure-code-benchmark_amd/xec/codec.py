@@ -119,6 +119,58 @@ def verify(d_data, d_parity, S: int, bs: int, k: int, m: int, d_flags, d_count=N
                                    _stream(stream)))
 
 
+def shard_table(shards):
+    """The host array of device pointers the shard calls take (h_shards): a
+    ctypes ``c_void_p`` array built from a sequence of tensors or integer
+    addresses, k data shards then m parity shards.  None stays None (a NULL
+    table); an array built here before is passed through."""
+    if shards is None or isinstance(shards, ctypes.Array):
+        return shards
+    return (ctypes.c_void_p * len(shards))(*[_ptr(s) for s in shards])
+
+
+def check_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int,
+                 m: int) -> Status:
+    """xec_check_shards -- the host-only check of a shard table (no GPU, no init):
+    sizes, alignment, strides and the overlap rule of include/xec.h."""
+    return Status(lib().xec_check_shards(shard_table(shards), data_stride, parity_stride, S, bs,
+                                         k, m))
+
+
+def encode_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int, m: int,
+                  stream=None) -> Status:
+    """xec_encode_shards -- xec_encode over one buffer per shard: block c of
+    shard i at shards[i] + c*stride (data_stride for the first k, parity_stride
+    for the m parity shards)."""
+    return Status(lib().xec_encode_shards(shard_table(shards), data_stride, parity_stride, S, bs,
+                                          k, m, _stream(stream)))
+
+
+def repair_shards_device(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int,
+                         m: int, d_bitmap, d_status, stream=None) -> Status:
+    """xec_repair_shards_device -- xec_repair_device over shards: every lost block
+    (d_bitmap byte 0), data or parity, rebuilt; the verdict lands in d_status."""
+    return Status(lib().xec_repair_shards_device(shard_table(shards), data_stride, parity_stride,
+                                                 S, bs, k, m, _ptr(d_bitmap), _ptr(d_status),
+                                                 _stream(stream)))
+
+
+def verify_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int, m: int,
+                  d_flags, d_count=None, stream=None) -> Status:
+    """xec_verify_shards -- the scrub over shards: d_flags[c*m + j] = 1 where
+    class j of stripe c no longer XORs to zero; d_count (optional) = how many."""
+    return Status(lib().xec_verify_shards(shard_table(shards), data_stride, parity_stride, S, bs,
+                                          k, m, _ptr(d_flags),
+                                          _ptr(d_count) if d_count is not None else None,
+                                          _stream(stream)))
+
+
+def shards_arg_capacity_used() -> int:
+    """xec_shards_arg_capacity_used: the pointer capacity (64 or 256) of this
+    thread's last shard call's kernel arguments; 0 if it launched nothing."""
+    return int(lib().xec_shards_arg_capacity_used())
+
+
 def update(d_data, d_parity, d_new, S: int, bs: int, k: int, m: int, h_items, n_items: int,
            d_scratch=None, scratch_bytes: int = 0, stream=None) -> Status:
     """xec_update -- in place: block i of stripe c takes the t-th block of d_new

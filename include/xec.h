@@ -240,6 +240,129 @@ int xec_repair_tiling_used(void);
 xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t bs, size_t k,
                       size_t m, uint8_t* d_flags, uint32_t* d_count, hipStream_t stream);
 
+/* ---- shard-major layout (no reference counterpart in its GPU codec; its
+ * Leopard, ISA-L and cm256 plugins take blocks as pointer tables for the same
+ * reason, src/algorithms/leopard_bm.cpp:24-47) -------------------------------
+ * A parity store keeps one buffer per shard -- per disk, failure domain or
+ * peer -- not the k + m blocks of a stripe side by side.  The calls below take
+ * that memory as it is: h_shards is a HOST array of k + m device pointers, the
+ * k data shards then the m parity shards, in the order of the bitmap's bytes,
+ * and
+ *   data block i   of stripe c : h_shards[i]     + c * data_stride     (i < k)
+ *   parity block j of stripe c : h_shards[k + j] + c * parity_stride   (j < m)
+ * The batch layout above is the special case h_shards[i] = d_data + i*bs,
+ * data_stride = k*bs, h_shards[k+j] = d_parity + j*bs, parity_stride = m*bs
+ * (hence two strides), and gives the bytes of the batch calls.  The table
+ * travels by value in the kernel arguments (64 or 256 pointers, 512 B or
+ * 2 KiB, the smaller that holds it): nothing is copied, no scratch is needed,
+ * and h_shards is read before the call returns -- there is no other host
+ * work, so every call is capturable, and a replay uses the pointers of the
+ * capture.  Shard forms exist for encode, the device-bitmap repair and the
+ * scrub; digest, locate, read, write and update are batch-only so far.
+ * When to use which (tools/shards_bench.py on one MI355X, configs 2, 3 and 4 --
+ * 8+1 x 64 KiB x 1,024, 16+1 x 1 MiB x 256, 32+1 x 4 KiB x 65,536; kernel
+ * times, round-to-round spreads 0.04-1.5 % and one of 2.9 %; DESIGN.md §3
+ * *Shard layout*): a caller whose bytes are already in the batch layout keeps
+ * the batch calls -- through a table aliased into the same batch the shard
+ * kernels took 0.99-1.01 of their time, except the scrub at config 2 and the
+ * repair of one data block per stripe at config 4, 1.08 both.  A caller with
+ * one buffer per shard uses these calls on that memory rather than copying into
+ * a batch and back: k + m separate allocations at stride bs took 1.00-1.13 of
+ * the batch calls' time, where the copy alone moves the same bytes twice more.
+ * Padding the stride by 4 KiB is not advice that holds: against stride bs it
+ * was 4-6 % faster at config 2, 15-17 % slower at config 3 and 6-9 % slower at
+ * config 4 (3 % faster for the data-block repair there).  Column rotation
+ * (xec_set_rotation(3)) on separate allocations made the scrub at config 3 4 %
+ * faster and everything else 0-4 % slower: leave it off.
+ *
+ * xec_check_shards: the host-only check the three compute calls run (no GPU
+ * and no xec_init needed).  In this order:
+ *  1. bs, then k and m, exactly as xec_check_args with both pointers NULL ->
+ *     XEC_INVALID_SIZE, XEC_INVALID_COUNTS;
+ *  2. S == 0 -> XEC_SUCCESS (h_shards is not looked at);
+ *  3. k + m > 256 -> XEC_INVALID_SIZE;
+ *  4. h_shards NULL, or an entry NULL -> XEC_INVALID_SIZE;
+ *  5. an entry not 64-byte aligned, or a stride not a multiple of 64 ->
+ *     XEC_INVALID_ALIGNMENT;
+ *  6. a stride < bs, or (S-1)*stride + bs not representable in 64 bits (or a
+ *     shard whose bytes would wrap the address space) -> XEC_INVALID_SIZE;
+ *  7. overlap -> XEC_INVALID_SIZE.  The hull of shard x is
+ *     [p_x, p_x + (S-1)*s_x + bs).  Every pair of shards must either have
+ *     disjoint hulls, or have the same stride s and, with
+ *     d = (p_y - p_x) mod s, both d >= bs and s - d >= bs: interleaved shards,
+ *     the batch layout among them.  A pair with different strides (a data
+ *     shard against a parity shard) must have disjoint hulls.
+ * The rule is conservative by design: it refuses some tables whose blocks do
+ * not in fact overlap (hulls that intersect at different strides, or at equal
+ * strides for a stripe count too small for the blocks to meet), and it holds
+ * encode's read-only data shards to the same rule, so that one rule covers
+ * all three calls.  The pair check is quadratic in k + m; tools/shards_bench.py
+ * reports what it costs per call at k + m = 17 and 256. */
+xec_status xec_check_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                            size_t S, size_t bs, size_t k, size_t m);
+
+/* xec_encode over shards: parity block j of stripe c = XOR of the data blocks
+ * i % m == j of stripe c, for every c < S.  Checks, in this order:
+ * XEC_NOT_INITIALIZED; xec_check_shards; S == 0 is XEC_SUCCESS with nothing
+ * queued.  Reads the k data shards' blocks, fully overwrites the m parity
+ * shards' blocks; bytes of a shard between its blocks (stride > bs) are never
+ * touched.  One kernel over class tiles, encode's: same launch shape
+ * (xec_set_launch, all four arguments), same column rotation (xec_set_rotation
+ * -- a permutation of a block's chunks, independent of the layout), parity
+ * stored nt, residency by xec_encode's table -- which was swept on the batch
+ * layout and has not been swept on this one. */
+xec_status xec_encode_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, hipStream_t stream);
+
+/* xec_repair_device over shards (it covers decode, and puts lost parity back):
+ * d_bitmap, d_status, the verdict and the all-or-nothing behaviour are
+ * xec_repair_device's -- *d_status = 0, the same check kernel (*d_status = 4 if
+ * a class of a stripe lost two blocks), then a repair kernel over class tiles
+ * that does nothing if *d_status != 0 and otherwise rebuilds every lost block,
+ * data or parity, from the other k/m blocks of its class.  Checks, in this
+ * order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_status NULL or not 4-byte aligned -> XEC_INVALID_ALIGNMENT; d_bitmap
+ *     NULL with S > 0 -> XEC_INVALID_SIZE;
+ *  4. S == 0 -> XEC_SUCCESS with only *d_status = 0 queued;
+ *  5. steps 3 to 7 of xec_check_shards.
+ * A rejected call queues nothing.  Blocks that are present, the bytes between
+ * blocks and the bitmap are never written; what a lost block holds on entry is
+ * irrelevant.  Launch shape, rotation and residency as xec_encode_shards; a
+ * rebuilt data block is stored sc1, a rebuilt parity block nt. */
+xec_status xec_repair_shards_device(const void* const* h_shards, size_t data_stride,
+                                    size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                    const uint8_t* d_bitmap, int32_t* d_status, hipStream_t stream);
+
+/* xec_verify over shards: d_flags (S*m device bytes, index c*m + j), d_count
+ * (device uint32 or NULL), what is flagged and what cannot be seen are
+ * xec_verify's.  Checks, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_count not 4-byte aligned -> XEC_INVALID_ALIGNMENT; d_flags NULL with
+ *     S > 0 -> XEC_INVALID_SIZE;
+ *  4. S == 0 -> XEC_SUCCESS with only *d_count = 0 queued (when given);
+ *  5. steps 3 to 7 of xec_check_shards.
+ * A rejected call queues nothing.  Reads every block of every shard once and
+ * writes nothing but d_flags and *d_count.  Residency by xec_verify's table,
+ * swept on the batch layout only.
+ * Captured in a hipGraph the two memsets become memset nodes.  Open
+ * observation (cause not found; tools/lab/graph_verify_probe.py, DESIGN.md §3
+ * *Update*): where the process allocated device memory, uploaded from pageable
+ * host memory or captured another graph around the capture, replays have left
+ * d_flags and *d_count with bytes no kernel stores, on a batch that was right.
+ * Run the scrub on a plain stream. */
+xec_status xec_verify_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, uint8_t* d_flags,
+                             uint32_t* d_count, hipStream_t stream);
+
+/* Diagnostics: how many pointers the kernel-argument table of the calling
+ * thread's most recent xec_encode_shards, xec_repair_shards_device or
+ * xec_verify_shards could hold -- 64 or 256, the smaller capacity that holds
+ * k + m; 0 when that call launched nothing (an error, or S == 0). */
+int xec_shards_arg_capacity_used(void);
+
 /* In-place block update, the small write of a parity store (no reference
  * counterpart: its codec encodes and decodes whole stripes).  Data block i of
  * stripe c is replaced by a new block and the parity of its class follows by
@@ -989,7 +1112,8 @@ int xec_decode_arg_capacity_used(void);
  * xec_decode_per_stripe, xec_decode_device, xec_decode_device_list,
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
  * xec_digest, xec_locate, xec_read, xec_read_device, xec_readv, xec_readv_device, xec_update_range,
- * xec_update_range_device, xec_write or xec_write_device call
+ * xec_update_range_device, xec_encode_shards, xec_repair_shards_device,
+ * xec_verify_shards, xec_write or xec_write_device call
  * launches its encode / decode / repair / verify / update / digest / read / write kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution
