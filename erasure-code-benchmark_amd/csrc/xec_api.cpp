@@ -1374,6 +1374,142 @@ xec_status xec_verify_shards(const void* const* h_shards, size_t data_stride, si
   return XEC_SUCCESS;
 }
 
+// xec_digest_shards / xec_locate_shards / xec_read_shards_device: the digest, the
+// locate and the device-resident degraded read over the same table.  Launch
+// shape and residency are the batch calls' (digest_launch_shape: uncapped;
+// read_occupancy: the table of a reconstruct tile), both defined with those
+// calls further down and, again, swept on the batch layout only.
+static xec::LaunchShape digest_launch_shape(size_t bs);
+static int read_occupancy(uint64_t nm, size_t n_lost);
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb);
+
+// Step 3 of xec_digest_shards (locate = false) and xec_locate_shards: the call's
+// own pointers and sizes, in digest_check's order.
+static xec_status digest_shards_check(size_t S, size_t k, size_t m, const void* d_digests,
+                                      const void* d_work, size_t work_bytes, bool locate,
+                                      const void* d_bitmap, const void* d_count) {
+  if (S != 0 && d_digests == nullptr) return XEC_INVALID_SIZE;
+  if (locate && ((S != 0 && d_work == nullptr) || work_bytes < xec_locate_work_bytes(S, k, m)))
+    return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_digests) % 8 != 0 ||
+      reinterpret_cast<uintptr_t>(d_work) % 8 != 0 || reinterpret_cast<uintptr_t>(d_count) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (locate && S != 0 && d_bitmap == nullptr) return XEC_INVALID_SIZE;
+  return XEC_SUCCESS;
+}
+
+xec_status xec_digest_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, const uint8_t* d_select,
+                             uint64_t* d_digests, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  st = digest_shards_check(S, k, m, d_digests, nullptr, 0, false, nullptr, nullptr);
+  if (st != XEC_SUCCESS) return st;
+  if (S == 0) return XEC_SUCCESS;
+  st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  const xec::LaunchShape ls = digest_launch_shape(bs);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  const hipError_t e = xec::launch_digest_shards(h_shards, data_stride, parity_stride, d_select,
+                                                 d_select ? xec::kDigestSelect : xec::kDigestAll,
+                                                 d_digests, g, ls, stream);
+  if (e != hipSuccess) return DEVERR(e);
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
+xec_status xec_locate_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, const uint64_t* d_digests,
+                             const uint8_t* d_flags, uint8_t* d_bitmap, uint32_t* d_count,
+                             void* d_work, size_t work_bytes, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  st = digest_shards_check(S, k, m, d_digests, d_work, work_bytes, true, d_bitmap, d_count);
+  if (st != XEC_SUCCESS) return st;
+  if (S != 0) {
+    st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+    if (st != XEC_SUCCESS) return st;
+  }
+  if (d_count != nullptr &&
+      hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  if (S == 0) return XEC_SUCCESS;
+  const xec::LaunchShape ls = digest_launch_shape(bs);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  uint64_t* fresh = static_cast<uint64_t*>(d_work);
+  hipError_t e = xec::launch_digest_shards(h_shards, data_stride, parity_stride, d_flags,
+                                           d_flags ? xec::kDigestFlags : xec::kDigestAll, fresh, g,
+                                           ls, stream);
+  if (e != hipSuccess) return DEVERR(e);
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  e = xec::launch_locate_compare(fresh, d_digests, d_flags, d_bitmap, d_count, g, stream);
+  return e == hipSuccess ? XEC_SUCCESS : DEVERR(e);
+}
+
+// Does [out, out + bytes) meet the hull of a shard of the (checked) table?
+// Ranges that only touch do not.
+static bool overlaps_a_shard_hull(const void* out, size_t bytes, const void* const* h_shards,
+                                  size_t data_stride, size_t parity_stride, size_t S, size_t bs,
+                                  size_t k, size_t m) {
+  for (size_t i = 0; i < k + m; ++i)
+    if (ranges_overlap(out, bytes, h_shards[i],
+                       (S - 1) * (i < k ? data_stride : parity_stride) + bs))
+      return true;
+  return false;
+}
+
+xec_status xec_read_shards_device(const void* const* h_shards, size_t data_stride,
+                                  size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                  const uint8_t* d_bitmap, const uint32_t* d_items,
+                                  size_t n_items, size_t offset, size_t len, void* d_out,
+                                  int32_t* d_status, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (n_items != 0 && S != 0) {
+    // steps 4 to 7 of xec_read, then d_items' alignment
+    if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+    if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset > bs || len > bs - offset)
+      return XEC_INVALID_SIZE;
+    if (d_out == nullptr || d_items == nullptr) return XEC_INVALID_SIZE;
+    if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0) return XEC_INVALID_ALIGNMENT;
+    if (reinterpret_cast<uintptr_t>(d_items) % 4 != 0) return XEC_INVALID_ALIGNMENT;
+    st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+    if (st != XEC_SUCCESS) return st;
+    if (n_items > SIZE_MAX / len ||
+        overlaps_a_shard_hull(d_out, n_items * len, h_shards, data_stride, parity_stride, S, bs, k,
+                              m))
+      return XEC_INVALID_SIZE;
+  }
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  if (n_items == 0 || S == 0) return XEC_SUCCESS;
+  // No host view of the bitmap: the table of a reconstruct tile (read_occupancy).
+  const xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, d_bitmap ? 1 : 0));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_read_check(d_bitmap, d_items, n_items, g, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  const hipError_t le =
+      xec::launch_read_shards(h_shards, data_stride, parity_stride, d_out, g, ls, offset, len,
+                              n_items, d_items, d_bitmap, stream);
+  if (le != hipSuccess) return DEVERR(le);
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
 // ---- in-place block update -----------------------------------------------------
 // xec_update / xec_update_device: parity[c][i % m] ^= data[c][i] ^ new, then
 // data[c][i] = new, for the named blocks only (xec_kernels.hip, update).  The

@@ -111,7 +111,7 @@ hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hip
 }
 
 // The codec kernels (encode, every decode, repair and update tiling, verify,
-// digest, read, ranged update, degraded write, the shard-layout three) go through this: as launch(), but with the thread's pending kernel events,
+// digest, read, ranged update, degraded write, the shard-layout kernels) go through this: as launch(), but with the thread's pending kernel events,
 // if any, recorded by the kernel's dispatch itself and then cleared.
 template <typename... P>
 hipError_t launch_codec(void (*kernel)(P...), dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
@@ -360,6 +360,17 @@ hipError_t launch_repair_shards(const void* const* h_shards, uint64_t dstride, u
 hipError_t launch_verify_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
                                 uint8_t* d_flags, const Geometry& g, const LaunchShape& ls,
                                 hipStream_t s);
+// launch_digest and launch_read with kReadDevTiles (g.gate must be set) over a
+// shard table: arguments, zeroing, tiles and grid as there, a block's address
+// from the table.  launch_locate_compare and launch_read_check touch no block
+// and serve both layouts.
+hipError_t launch_digest_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const uint8_t* d_gate, int mode, uint64_t* d_out,
+                                const Geometry& g, const LaunchShape& ls, hipStream_t s);
+hipError_t launch_read_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                              void* d_out, const Geometry& g, const LaunchShape& ls,
+                              uint64_t offset, uint64_t len, uint64_t n_items,
+                              const uint32_t* d_items, const uint8_t* d_bitmap, hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

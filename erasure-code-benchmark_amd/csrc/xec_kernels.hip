@@ -2757,6 +2757,175 @@ __global__ __launch_bounds__(T) void verify_shards_kernel(uint8_t* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Shard-major digest, locate and degraded read (xec_digest_shards,
+// xec_locate_shards, xec_read_shards_device): digest_kernel and read_dev_kernel
+// with a block's address taken from the shard table,
+//   block i of stripe c : tab.v[i] + c * (i < k ? dstride : pstride)
+// -- the tile's block index is uniform per workgroup, so that is one scalar
+// load from the argument segment and a scalar multiply-add per tile.  Segments,
+// loads in flight, the reduction and its one 64-bit atomic add per (block,
+// segment), the gate, the range tiles, the store through the item's slot: all
+// theirs.  digest_zero_kernel, locate_compare_kernel and read_check_kernel touch
+// no block and serve both layouts.  Emitted after everything above, which stays
+// instruction for instruction what it was.
+// ---------------------------------------------------------------------------
+template <bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void digest_shards_kernel(const uint8_t* __restrict__ gate,
+                                                          int mode, uint64_t* out, Geometry g,
+                                                          uint64_t dstride, uint64_t pstride,
+                                                          ShardTab<CAP> tab) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  constexpr uint64_t kStepZ = (uint64_t)(2 * T) * kSplitmixGolden;  // 2*T words per step
+  constexpr int kInFlight = 8;                                      // as digest_kernel
+  __shared__ uint64_t wave_sum[T / 64];
+  const uint64_t tot = g.k + g.m;
+  for (uint64_t t = blockIdx.x; t < g.total_tiles; t += gridDim.x) {
+    const uint64_t seg = t % g.tiles_per_block, b = t / g.tiles_per_block;
+    const uint64_t c = b / tot, i = b % tot;
+    if (!digest_wanted(gate, mode, c, i, g)) continue;  // uniform: scalar loads only
+    const uint8_t* blk = tab.v[i] + c * (i < g.k ? dstride : pstride);
+    const uint64_t begin = seg * kDigestSegmentBytes;
+    const uint64_t end = g.bs - begin < kDigestSegmentBytes ? g.bs : begin + kDigestSegmentBytes;
+    uint64_t off = begin + threadIdx.x * 16ull;
+    uint64_t z = (off / 8 + 1) * kSplitmixGolden;  // (n + 1) * golden of this lane's first word
+    uint64_t acc = 0;
+    for (; off + (kInFlight - 1) * kStep < end; off += kInFlight * kStep, z += kInFlight * kStepZ) {
+      u32x4 v[kInFlight];
+#pragma unroll
+      for (int q = 0; q < kInFlight; ++q) v[q] = ld16<NT>(blk + off + q * kStep);
+#pragma unroll
+      for (int q = 0; q < kInFlight; ++q) acc += digest_granule(v[q], z + q * kStepZ);
+    }
+    // the tail issues every load before the first multiply, as digest_kernel's
+    if (off < end) {
+      u32x4 v[kInFlight - 1];
+#pragma unroll
+      for (int q = 0; q < kInFlight - 1; ++q)
+        if (off + q * kStep < end) v[q] = ld16<NT>(blk + off + q * kStep);
+#pragma unroll
+      for (int q = 0; q < kInFlight - 1; ++q)
+        if (off + q * kStep < end) acc += digest_granule(v[q], z + q * kStepZ);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d);
+    if constexpr (T > 64) {  // the tile loop is uniform per workgroup: every wave gets here
+      if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = acc;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        acc = 0;
+#pragma unroll
+        for (int w = 0; w < T / 64; ++w) acc += wave_sum[w];
+      }
+      __syncthreads();  // wave_sum is free for the next tile
+    }
+    if (threadIdx.x == 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(out + b), (unsigned long long)acc);
+  }
+}
+
+// xor_shard_members with the store left to the caller: to xor_shard_members what
+// xor_members_to is to xor_members (and a copy for the reason given there).
+// store(o, v) takes the granule at block offset o; `end` is the end of what the
+// tile may touch, the range's end inside the block.
+template <int NM, int U, bool NT, int T, uint32_t CAP, typename Store>
+__device__ __forceinline__ void xor_shard_members_to(const ShardTab<CAP>& tab, uint64_t first,
+                                                     uint64_t m, uint64_t doff,
+                                                     const uint8_t* sub, int subst, uint64_t off,
+                                                     uint64_t end, uint32_t nm_rt, Store store) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  if constexpr (NM > 0) {
+    const bool whole = off + (U - 1) * kStep < end;  // the tile's last granule row is in the range
+    if (whole) {
+      u32x4 v[NM][U];
+#pragma unroll
+      for (int r = 0; r < NM; ++r) {
+        const uint8_t* src = (r == subst ? sub : tab.v[first + (uint64_t)r * m] + doff) + off;
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[r][u] = ld16<NT>(src + u * kStep);
+      }
+      if constexpr (NM >= 32) __builtin_amdgcn_sched_barrier(0);  // as xor_members
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        u32x4 acc = v[0][u];
+#pragma unroll
+        for (int r = 1; r < NM; ++r) acc ^= v[r][u];
+        store(off + u * kStep, acc);
+      }
+      return;
+    }
+  }
+  // Ragged tail of the range, or a member count without a compiled unroll.
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : nm_rt;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint64_t o = off + u * kStep;
+    if (o >= end) continue;
+    u32x4 acc = {0u, 0u, 0u, 0u};
+    uint32_t r = 0;
+    for (; r + 8 <= nm; r += 8) {
+      u32x4 v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int rr = (int)(r + q);
+        v[q] = ld16<NT>((rr == subst ? sub : tab.v[first + (uint64_t)rr * m] + doff) + o);
+      }
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc ^= v[q];
+    }
+    for (; r < nm; ++r)
+      acc ^= ld16<NT>(((int)r == subst ? sub : tab.v[first + (uint64_t)r * m] + doff) + o);
+    store(o, acc);
+  }
+}
+
+// read_dev_kernel over a shard table: gated on read_check_kernel's verdict (so
+// every item it sees is in range -- i < k + m <= CAP -- and servable), the
+// verdict of an item its own bitmap byte, tiles walked from the end of the list.
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void read_shards_kernel(uint8_t* out,
+                                                        const uint32_t* __restrict__ items,
+                                                        const uint8_t* __restrict__ bitmap,
+                                                        ReadRange rr, Geometry g, uint64_t dstride,
+                                                        uint64_t pstride, ShardTab<CAP> tab) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint32_t m = (uint32_t)g.m, k = (uint32_t)g.k;
+  const uint64_t end = rr.offset + rr.len;
+  const uint32_t len = (uint32_t)rr.len;
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;
+    const uint64_t e = t / g.tiles_per_block, chunk = t % g.tiles_per_block;
+    const uint32_t item = *(const_u32_as4)(items + e);
+    const uint64_t c = item >> 8;
+    const uint32_t i = item & 0xFFu;
+    const bool lost = bitmap != nullptr &&
+                      sbyte(reinterpret_cast<uint64_t>(bitmap) + c * (g.k + g.m) + i) == 0;
+    const uint64_t off = rr.offset + (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+    uint8_t* slot = out + e * rr.len;
+    auto store = [&](uint64_t o, u32x4 v) { st16_slot<NT>(slot, len, o - rr.offset, v); };
+    if (!lost) {
+      const uint8_t* blk = tab.v[i] + c * (i < k ? dstride : pstride);
+      u32x4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (off + u * kStep < end) v[u] = ld16<NT>(blk + off + u * kStep);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (off + u * kStep < end) store(off + u * kStep, v[u]);
+      continue;
+    }
+    const uint32_t j = i < k ? i % m : i - k;  // the item's class
+    if (i < k)  // a data block: the other members and the class parity, as decode
+      xor_shard_members_to<NM, U, NT, T>(tab, j, g.m, c * dstride, tab.v[g.k + j] + c * pstride,
+                                         (int)(i / m), off, end, nm, store);
+    else  // a parity block: every data member, as encode
+      xor_shard_members_to<NM, U, NT, T>(tab, j, g.m, c * dstride, nullptr, -1, off, end, nm,
+                                         store);
+  }
+}
+
 namespace {
 
 // The k + m of h_shards in a ShardTab<CAP>, the rest null (never indexed).
@@ -2823,6 +2992,62 @@ hipError_t launch_verify_shards(const void* const* h_shards, uint64_t dstride, u
     constexpr uint32_t CAP = decltype(cap)::value;
     return launch_codec(verify_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s,
                         d_flags, g, dstride, pstride, shard_tab<CAP>(h_shards, g.k + g.m));
+  });
+}
+
+// launch_digest over a shard table: the same zeroing, tiles and grid.
+hipError_t launch_digest_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                                const uint8_t* d_gate, int mode, uint64_t* d_out,
+                                const Geometry& g_class, const LaunchShape& ls, hipStream_t s) {
+  Geometry g = g_class;
+  g.tiles_per_block = (g.bs + kDigestSegmentBytes - 1) / kDigestSegmentBytes;
+  g.total_tiles = g.S * (g.k + g.m) * g.tiles_per_block;
+  if (g.total_tiles == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g) || d_out == nullptr ||
+      (mode != kDigestAll && d_gate == nullptr) || mode < kDigestAll || mode > kDigestFlags)
+    return hipErrorInvalidValue;
+  const uint64_t slots = g.S * (g.k + g.m);
+  const hipError_t e =
+      mode == kDigestAll
+          ? hipMemsetAsync(d_out, 0, slots * sizeof(uint64_t), s)
+          : launch(digest_zero_kernel, grid_for((slots + 255) / 256, 8192, 256), 256, 0, s, d_gate,
+                   mode, d_out, g);
+  if (e != hipSuccess) return e;
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_bool(ls.nt, [&](auto ntc) {
+    constexpr bool NT = decltype(ntc)::value;
+    return with_shard_capacity(g.k + g.m, [&](auto cap) {
+      constexpr uint32_t CAP = decltype(cap)::value;
+      const ShardTab<CAP> tab = shard_tab<CAP>(h_shards, g.k + g.m);
+      if (ls.threads == 256)
+        return launch_codec(digest_shards_kernel<NT, 256, CAP>, grid, 256, ls.lds_bytes, s, d_gate,
+                            mode, d_out, g, dstride, pstride, tab);
+      return launch_codec(digest_shards_kernel<NT, 64, CAP>, grid, 64, ls.lds_bytes, s, d_gate,
+                          mode, d_out, g, dstride, pstride, tab);
+    });
+  });
+}
+
+// launch_read with kReadDevTiles over a shard table (g.gate must be set).
+hipError_t launch_read_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                              void* d_out, const Geometry& g_class, const LaunchShape& ls,
+                              uint64_t offset, uint64_t len, uint64_t n_items,
+                              const uint32_t* d_items, const uint8_t* d_bitmap, hipStream_t s) {
+  if (n_items == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g_class) || d_out == nullptr || d_items == nullptr || len == 0 ||
+      offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs || g_class.gate == nullptr)
+    return hipErrorInvalidValue;
+  const Geometry g = range_geometry(g_class, ls, len, n_items);
+  const ReadRange rr{offset, len};
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_shard_shape(g, ls, [&](auto sh, auto cap) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch_codec(read_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s, out,
+                        d_items, d_bitmap, rr, g, dstride, pstride,
+                        shard_tab<CAP>(h_shards, g.k + g.m));
   });
 }
 

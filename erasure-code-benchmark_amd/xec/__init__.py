@@ -22,7 +22,8 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     check_write_items, write, write_device, write_scratch_bytes,
                     write_tiling_used,
                     check_shards, encode_shards, repair_shards_device, shard_table,
-                    shards_arg_capacity_used, verify_shards)
+                    shards_arg_capacity_used, verify_shards,
+                    digest_shards, locate_shards, read_shards_device)
 from .partition import stripe_range
 
 __all__ = [
@@ -44,4 +45,5 @@ __all__ = [
     "check_write_items", "write", "write_device", "write_scratch_bytes", "write_tiling_used",
     "check_shards", "encode_shards", "repair_shards_device", "shard_table",
     "shards_arg_capacity_used", "verify_shards",
+    "digest_shards", "locate_shards", "read_shards_device",
 ]

@@ -42,6 +42,7 @@ EXPORTED = (
     "xec_write_tiling_used",
     "xec_check_shards", "xec_encode_shards", "xec_repair_shards_device", "xec_verify_shards",
     "xec_shards_arg_capacity_used",
+    "xec_digest_shards", "xec_locate_shards", "xec_read_shards_device",
 )
 
 
@@ -158,6 +159,10 @@ def lib() -> ctypes.CDLL:
         "xec_repair_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_verify_shards": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp], st),
         "xec_shards_arg_capacity_used": ([], ctypes.c_int),
+        "xec_digest_shards": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp], st),
+        "xec_locate_shards": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, sz, vp], st),
+        "xec_read_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp],
+                                   st),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

@@ -165,6 +165,45 @@ def verify_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int,
                                           _stream(stream)))
 
 
+def digest_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int, m: int,
+                  d_digests, d_select=None, stream=None) -> Status:
+    """xec_digest_shards -- xec_digest over shards: d_digests (S*(k+m) device
+    uint64, the bitmap's layout) = the digest of every block, or of those
+    d_select (S*(k+m) device bytes, nonzero = digest) picks."""
+    return Status(lib().xec_digest_shards(shard_table(shards), data_stride, parity_stride, S, bs,
+                                          k, m, _ptr(d_select) if d_select is not None else None,
+                                          _ptr(d_digests), _stream(stream)))
+
+
+def locate_shards(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int, m: int,
+                  d_digests, d_flags, d_bitmap, d_count, d_work, work_bytes: int,
+                  stream=None) -> Status:
+    """xec_locate_shards -- xec_locate over shards: d_bitmap = 0 where a block's
+    digest differs from d_digests, else 1 (d_flags None: every block, else the
+    classes verify_shards flagged); what repair_shards_device takes."""
+    return Status(lib().xec_locate_shards(shard_table(shards), data_stride, parity_stride, S, bs,
+                                          k, m, _ptr(d_digests),
+                                          _ptr(d_flags) if d_flags is not None else None,
+                                          _ptr(d_bitmap),
+                                          _ptr(d_count) if d_count is not None else None,
+                                          _ptr(d_work), work_bytes, _stream(stream)))
+
+
+def read_shards_device(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int,
+                       m: int, d_bitmap, d_items, n_items: int, offset: int, length: int, d_out,
+                       d_status, stream=None) -> Status:
+    """xec_read_shards_device -- xec_read_device over shards: bytes [offset,
+    offset + length) of the blocks the device items c << 8 | i name go to d_out,
+    lost ones (d_bitmap byte 0; None = all present) reconstructed; the verdict
+    (0, 3 or 4) lands in d_status.  Capturable."""
+    return Status(lib().xec_read_shards_device(shard_table(shards), data_stride, parity_stride, S,
+                                               bs, k, m,
+                                               _ptr(d_bitmap) if d_bitmap is not None else None,
+                                               _ptr(d_items) if d_items is not None else None,
+                                               n_items, offset, length, _ptr(d_out),
+                                               _ptr(d_status), _stream(stream)))
+
+
 def shards_arg_capacity_used() -> int:
     """xec_shards_arg_capacity_used: the pointer capacity (64 or 256) of this
     thread's last shard call's kernel arguments; 0 if it launched nothing."""

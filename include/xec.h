@@ -257,8 +257,12 @@ xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t
  * 2 KiB, the smaller that holds it): nothing is copied, no scratch is needed,
  * and h_shards is read before the call returns -- there is no other host
  * work, so every call is capturable, and a replay uses the pointers of the
- * capture.  Shard forms exist for encode, the device-bitmap repair and the
- * scrub; digest, locate, read, write and update are batch-only so far.
+ * capture.  Shard forms exist for encode, the device-bitmap repair, the
+ * scrub, digest, locate and the device-resident degraded read; readv, write and
+ * update (xec_update, xec_update_range) are batch-only so far, and so are the
+ * host-list forms (xec_read, xec_repair, xec_decode).  Every table entry must be
+ * a valid shard in every call, a dead shard with no memory behind it included:
+ * a lost block is never read, but its address must still pass xec_check_shards.
  * When to use which (tools/shards_bench.py on one MI355X, configs 2, 3 and 4 --
  * 8+1 x 64 KiB x 1,024, 16+1 x 1 MiB x 256, 32+1 x 4 KiB x 65,536; kernel
  * times, round-to-round spreads 0.04-1.5 % and one of 2.9 %; DESIGN.md §3
@@ -274,6 +278,19 @@ xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t
  * config 4 (3 % faster for the data-block repair there).  Column rotation
  * (xec_set_rotation(3)) on separate allocations made the scrub at config 3 4 %
  * faster and everything else 0-4 % slower: leave it off.
+ * Digest, locate and read, same tool and configs (spreads 0.06-3.1 %, the batch
+ * locate at config 2 8 % and the batch digest at config 4 4.6 %): the digest
+ * and the locate over the flags of one class in 64 took 0.99-1.00 of the batch
+ * kernels' time aliased and 0.95-1.06 on separate allocations, padded or not.
+ * The read of one whole lost block per stripe took 1.01 / 0.97 / 1.09 aliased
+ * at configs 2 / 3 / 4 and 1.00 / 1.07 / 1.12 on separate allocations; 4 KiB
+ * from each of min(S, 1024) lost blocks 1.06 / 1.00 / 1.11 aliased (9.0, 5.8 and
+ * 26 us) and 1.04 / 1.11 / 1.12 separate.  The 1.09-1.12 at config 4 is the
+ * repair's 1.08 again: a tile there is 1 KiB of each of 32 members, and each
+ * member's address is a scalar load from the kernel arguments with a wait of
+ * its own where the batch kernel adds a stride.  A stride padded by 4 KiB,
+ * against stride bs, made the 4 KiB reads 18 % faster at config 2 and both
+ * reads 6-8 % slower at config 4.
  *
  * xec_check_shards: the host-only check the three compute calls run (no GPU
  * and no xec_init needed).  In this order:
@@ -357,10 +374,95 @@ xec_status xec_verify_shards(const void* const* h_shards, size_t data_stride, si
                              size_t S, size_t bs, size_t k, size_t m, uint8_t* d_flags,
                              uint32_t* d_count, hipStream_t stream);
 
+/* xec_digest over shards: d_digests (S*(k+m) device u64, the bitmap's layout),
+ * d_select (NULL = every block, else S*(k+m) device bytes, nonzero = digest
+ * this block; an unselected block is not read and its slot neither read nor
+ * written), the digest itself -- bit-exact against xec_digest_host -- and what
+ * zeroes the selected slots (a memset with d_select NULL, else a small kernel)
+ * are xec_digest's.  Checks, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_digests NULL with S > 0 -> XEC_INVALID_SIZE; d_digests not 8-byte
+ *     aligned -> XEC_INVALID_ALIGNMENT;
+ *  4. S == 0 -> XEC_SUCCESS with nothing queued;
+ *  5. steps 3 to 7 of xec_check_shards.
+ * A rejected call queues nothing.  Reads each selected block once -- bytes of a
+ * shard between its blocks (stride > bs) are never read -- and writes nothing
+ * but d_digests; through a table aliased into a batch it leaves exactly
+ * xec_digest's slots.  One kernel over (block, 64 KiB segment) tiles,
+ * xec_digest's: same grid limit, xec_set_launch as there (max_grid,
+ * cache_policy, block_threads), no column rotation, residency uncapped -- swept
+ * on the batch layout only. */
+xec_status xec_digest_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, const uint8_t* d_select,
+                             uint64_t* d_digests, hipStream_t stream);
+
+/* xec_locate over shards: d_digests (the stored digests), d_flags (NULL = check
+ * every block, else xec_verify_shards' S*m flags: the gate -- a block of an
+ * unflagged class is not read and reads 1), d_bitmap (S*(k+m) device bytes, 0 =
+ * the digest differs), d_count and d_work (xec_locate_work_bytes(S, k, m)
+ * bytes: the size serves both layouts) are xec_locate's, and so is what is
+ * queued: *d_count zeroed by a memset, the checked slots of d_work zeroed (a
+ * memset with d_flags NULL, else a small kernel), the digest kernel of
+ * xec_digest_shards, the compare-and-count kernel of xec_locate.  Checks, in
+ * this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_digests or d_work NULL with S > 0, or work_bytes too small ->
+ *     XEC_INVALID_SIZE; d_digests or d_work not 8-byte aligned, or d_count not
+ *     4-byte aligned -> XEC_INVALID_ALIGNMENT; d_bitmap NULL with S > 0 ->
+ *     XEC_INVALID_SIZE;
+ *  4. S == 0 -> XEC_SUCCESS with only *d_count = 0 queued (when given);
+ *  5. steps 3 to 7 of xec_check_shards.
+ * A rejected call queues nothing.  No shard is written and no byte between
+ * blocks is read; aliased into a batch it leaves exactly xec_locate's bitmap
+ * and count.  xec_verify_shards -> xec_locate_shards(flags) ->
+ * xec_repair_shards_device runs on one stream with no host step and no copy;
+ * the three outcomes for a flagged class are those listed at xec_locate.  A
+ * capture contains memset nodes: the open observation recorded at xec_verify
+ * applies, run the chain on a plain stream. */
+xec_status xec_locate_shards(const void* const* h_shards, size_t data_stride, size_t parity_stride,
+                             size_t S, size_t bs, size_t k, size_t m, const uint64_t* d_digests,
+                             const uint8_t* d_flags, uint8_t* d_bitmap, uint32_t* d_count,
+                             void* d_work, size_t work_bytes, hipStream_t stream);
+
+/* xec_read_device over shards: serve reads from a store with a shard down.
+ * d_bitmap (NULL = everything present, a pure gather), d_items (c << 8 | i, any
+ * order, repeats allowed), the range rules, d_out (item t's bytes at d_out +
+ * t*len), the verdicts 0 / 3 / 4 left as a maximum in *d_status, and the
+ * all-or-nothing behaviour over the requested items are xec_read_device's, and
+ * so is what is queued: *d_status = 0 (a memset), the same check kernel over
+ * the items, then a read kernel that does nothing if *d_status != 0.  A lost
+ * block is never read, and nothing but d_out and *d_status is written: a
+ * reader needs no write access to the store.  Checks, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_status NULL or not 4-byte aligned -> XEC_INVALID_ALIGNMENT; n_items == 0
+ *     or S == 0 -> XEC_SUCCESS with only *d_status = 0 queued; steps 4 to 7 of
+ *     xec_read with d_items in h_items' place; d_items not 4-byte aligned ->
+ *     XEC_INVALID_ALIGNMENT;
+ *  4. steps 3 to 7 of xec_check_shards;
+ *  5. d_out's n_items*len bytes intersect the hull [p_x, p_x + (S-1)*s_x + bs)
+ *     of any shard -> XEC_INVALID_SIZE.  The conservative hull rule of
+ *     xec_check_shards: a d_out placed in a gap between two blocks of one shard
+ *     is refused; ranges that only touch are allowed.
+ * A rejected call queues nothing.  Bytes of a shard between its blocks are
+ * never read; aliased into a batch it delivers exactly xec_read_device's bytes.
+ * Capturable (one memset node, for *d_status).  One kernel over (item, chunk of
+ * the range) tiles, xec_read_device's: xec_set_launch as there, no column
+ * rotation, residency by xec_read_device's table, swept on the batch layout
+ * only. */
+xec_status xec_read_shards_device(const void* const* h_shards, size_t data_stride,
+                                  size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                  const uint8_t* d_bitmap, const uint32_t* d_items,
+                                  size_t n_items, size_t offset, size_t len, void* d_out,
+                                  int32_t* d_status, hipStream_t stream);
+
 /* Diagnostics: how many pointers the kernel-argument table of the calling
- * thread's most recent xec_encode_shards, xec_repair_shards_device or
- * xec_verify_shards could hold -- 64 or 256, the smaller capacity that holds
- * k + m; 0 when that call launched nothing (an error, or S == 0). */
+ * thread's most recent shard call (xec_encode_shards, xec_repair_shards_device,
+ * xec_verify_shards, xec_digest_shards, xec_locate_shards or
+ * xec_read_shards_device) could hold -- 64 or 256, the smaller capacity that holds
+ * k + m; 0 when that call launched nothing (an error, S == 0, or no items). */
 int xec_shards_arg_capacity_used(void);
 
 /* In-place block update, the small write of a parity store (no reference
@@ -1113,7 +1215,8 @@ int xec_decode_arg_capacity_used(void);
  * xec_repair, xec_repair_device, xec_verify, xec_update, xec_update_device,
  * xec_digest, xec_locate, xec_read, xec_read_device, xec_readv, xec_readv_device, xec_update_range,
  * xec_update_range_device, xec_encode_shards, xec_repair_shards_device,
- * xec_verify_shards, xec_write or xec_write_device call
+ * xec_verify_shards, xec_digest_shards, xec_locate_shards,
+ * xec_read_shards_device, xec_write or xec_write_device call
  * launches its encode / decode / repair / verify / update / digest / read / write kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution

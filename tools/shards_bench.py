@@ -3,9 +3,12 @@
 
 For configs 2, 3 and 4 of BASELINE.json each operation -- encode, the scrub, the
 device repair with every parity block lost and with one data block lost per
-stripe -- runs in four placements of the same bytes:
+stripe; the digest of every block, the locate over the flags of one class in
+64, the degraded read of one whole lost block per stripe and of 4 KiB from each
+of min(S, 1024) lost blocks -- runs in four placements of the same bytes:
 
-  batch    the existing batch call (xec_encode, xec_verify, xec_repair_device);
+  batch    the existing batch call (xec_encode, xec_verify, xec_repair_device,
+           xec_digest, xec_locate, xec_read_device);
   alias    the shard call on pointers aliased into that same batch: the same
            addresses, so the difference is the cost of table addressing alone;
   sep      k + m separate allocations, stride = bs;
@@ -13,14 +16,16 @@ stripe -- runs in four placements of the same bytes:
 
 `sep` puts the members of a class S*bs apart, a large power of two -- the access
 pattern column rotation exists for -- so it also runs with rotation off
-(sep_rot-1) and on (sep_rot3).
+(sep_rot-1) and on (sep_rot3); rotation applies to none of digest, locate and
+read, which run in the four placements only.
 
 Kernel times come from each call's own dispatch (xec_set_kernel_events).  The
 placements of an operation are interleaved round by round; a figure is the
 median of a round's launches after three warm-up launches, and every placement
 reports its own spread over the rounds ((max - min) / median): a difference
 inside the spreads of the two sides is not a difference.  After the timed
-launches of a placement its store is scrubbed: the count must be 0.
+launches of a placement its store is scrubbed: the count must be 0, and what
+a digest, locate or read left must equal what the batch call left.
 
 Host cost: the time one xec_encode_shards call takes to return (checks, pair
 check, launch) at k + m = 17 and 256, beside xec_encode and beside
@@ -29,7 +34,8 @@ xec_check_shards alone, on a tiny batch.
 Every GPU step runs under a time limit of its own (--step-timeout): a step that
 overruns ends the process with a traceback instead of queueing more work.
 
-    python tools/shards_bench.py [--rounds 3] [--iters 20] [--only cfg3] [--out f.json]
+    python tools/shards_bench.py [--rounds 3] [--iters 20] [--only cfg3] [--ops digest,read_4k]
+                                 [--out f.json]
 """
 from __future__ import annotations
 
@@ -48,7 +54,10 @@ sys.path.insert(0, str(ROOT / "erasure-code-benchmark_amd"))
 CONFIGS = {"cfg2": (8, 1, 1 << 16, 1024), "cfg3": (16, 1, 1 << 20, 256),
            "cfg4": (32, 1, 4096, 65536)}  # k, m, bs, S (bench.py WORKLOADS)
 PAD = 4096
-OPS = ["encode", "verify", "repair_parity", "repair_data"]
+OPS = ["encode", "verify", "repair_parity", "repair_data", "digest", "locate_flags", "read_block",
+       "read_4k"]
+NO_ROTATION = OPS[4:]  # xec_set_rotation applies to none of these
+READ_4K_ITEMS, READ_4K_LEN = 1024, 4096
 
 
 @contextmanager
@@ -91,9 +100,49 @@ class Placement:
         self.flags = torch.empty(S * m, dtype=torch.uint8, device="cuda")
         self.count = torch.zeros(1, dtype=torch.int32, device="cuda")
         self.status = torch.zeros(1, dtype=torch.int32, device="cuda")
+        n = S * (k + m)
+        self.digests = torch.empty(n, dtype=torch.int64, device="cuda")
+        self.work = torch.empty(n, dtype=torch.int64, device="cuda")
+        self.bitmap = torch.empty(n, dtype=torch.uint8, device="cuda")
+        self.out = torch.empty(S * bs, dtype=torch.uint8, device="cuda")
+
+    def result(self, op):
+        """What the last `op` left, for the comparison with the batch call's."""
+        if op == "digest":
+            return self.digests
+        if op == "locate_flags":
+            return self.torch.cat([self.bitmap, self.count.view(self.torch.uint8)])
+        n = self.S * self.bs if op == "read_block" else min(self.S, READ_4K_ITEMS) * READ_4K_LEN
+        return self.out[:n]
+
+    def call_integrity(self, op, bm, s):
+        x, a = self.xec, (self.S, self.bs, self.k, self.m)
+        if self.batch is not None:
+            d, p = self.batch
+            if op == "digest":
+                return x.digest(d, p, *a, self.digests, None, s)
+            if op == "locate_flags":
+                return x.locate(d, p, *a, bm["stored"], bm["flags64"], self.bitmap, self.count,
+                                self.work, 8 * self.work.numel(), s)
+            n, length = (self.S, self.bs) if op == "read_block" else \
+                (min(self.S, READ_4K_ITEMS), READ_4K_LEN)
+            return x.read_device(d, p, *a, bm["repair_data"], bm["items"], n, 0, length, self.out,
+                                 self.status, s)
+        t = (self.table, self.ds, self.ps)
+        if op == "digest":
+            return x.digest_shards(*t, *a, self.digests, None, s)
+        if op == "locate_flags":
+            return x.locate_shards(*t, *a, bm["stored"], bm["flags64"], self.bitmap, self.count,
+                                   self.work, 8 * self.work.numel(), s)
+        n, length = (self.S, self.bs) if op == "read_block" else \
+            (min(self.S, READ_4K_ITEMS), READ_4K_LEN)
+        return x.read_shards_device(*t, *a, bm["repair_data"], bm["items"], n, 0, length, self.out,
+                                    self.status, s)
 
     def call(self, op, bm, s):
         x, a = self.xec, (self.S, self.bs, self.k, self.m)
+        if op in NO_ROTATION:
+            return self.call_integrity(op, bm, s)
         if self.batch is not None:
             d, p = self.batch
             if op == "encode":
@@ -133,7 +182,7 @@ def label(pl: Placement):
     return pl.name if pl.rotation == 0 else f"{pl.name}_rot{pl.rotation}"
 
 
-def run_config(xec, torch, name, shape, rounds, iters, lim):
+def run_config(xec, torch, name, shape, rounds, iters, lim, ops):
     import numpy as np
     k, m, bs, S = shape
     s = torch.cuda.current_stream()
@@ -153,14 +202,23 @@ def run_config(xec, torch, name, shape, rounds, iters, lim):
         data = np.ones((S, k + m), np.uint8)
         for c in range(S):
             data[c, (7 * c) % k] = 0
+        # the lost data block of every stripe, in stripe order; one class flag in 64
+        items = np.array([(c << 8) | ((7 * c) % k) for c in range(S)], np.uint32)
+        flags64 = np.zeros(S * m, np.uint8)
+        flags64[::64] = 1
+        stored = torch.empty(S * (k + m), dtype=torch.int64, device="cuda")
+        assert xec.digest(d, p, S, bs, k, m, stored, None, s) == 0
         bm = {"repair_parity": torch.from_numpy(parity.reshape(-1)).to("cuda"),
-              "repair_data": torch.from_numpy(data.reshape(-1)).to("cuda")}
+              "repair_data": torch.from_numpy(data.reshape(-1)).to("cuda"),
+              "items": torch.from_numpy(items.view(np.int32)).to("cuda"),
+              "flags64": torch.from_numpy(flags64).to("cuda"), "stored": stored}
         torch.cuda.synchronize()
     rows = []
-    for op in OPS:
-        per = {label(pl): [] for pl in pls}
+    for op in ops:
+        timed = pls[:4] if op in NO_ROTATION else pls
+        per = {label(pl): [] for pl in timed}
         for r in range(rounds):
-            for pl in pls:
+            for pl in timed:
                 with step(lim, f"{name} {op} round {r} {label(pl)}"):
                     per[label(pl)].append(pl.time_round(op, bm, iters, ev, s))
         med = {n: statistics.median(v) for n, v in per.items()}
@@ -174,6 +232,12 @@ def run_config(xec, torch, name, shape, rounds, iters, lim):
                 "GBps_of_batch_bytes": round((k + m) * bs * S / med[n] / 1e3, 1)}
         print(json.dumps(row), flush=True)
         rows.append(row)
+        if op in NO_ROTATION:
+            with step(lim, f"{name} {op}: every placement left what the batch call left"):
+                torch.cuda.synchronize()
+                assert int(pls[0].status.item()) == 0 and int(pls[0].count.item()) == 0
+                for pl in pls[1:4]:
+                    assert torch.equal(pl.result(op), pls[0].result(op)), f"{name} {op} {pl.name}"
     with step(lim, f"{name}: scrub every placement"):
         for pl in pls[:4]:
             assert pl.scrub_is_clean(s), f"{name} {pl.name}: not clean after the timed launches"
@@ -222,6 +286,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default="", help="comma list of cfg2,cfg3,cfg4,host (default: all)")
+    ap.add_argument("--ops", default="", help=f"comma list of {','.join(OPS)} (default: all)")
     ap.add_argument("--step-timeout", type=float, default=90.0)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -232,13 +297,15 @@ def main():
     torch.cuda.set_device(0)
     assert xec.init(0) == 0
     want = set(args.only.split(",")) if args.only else set(CONFIGS) | {"host"}
+    ops = [op for op in OPS if not args.ops or op in args.ops.split(",")]
+    assert ops and (not args.ops or set(args.ops.split(",")) <= set(OPS)), args.ops
     out = {"build_info": xec.build_info(), "rounds": args.rounds, "iters": args.iters, "rows": [],
            "host": []}
     print(json.dumps({"build_info": out["build_info"]}), flush=True)
     for name, shape in CONFIGS.items():
         if name in want:
             out["rows"] += run_config(xec, torch, name, shape, args.rounds, args.iters,
-                                      args.step_timeout)
+                                      args.step_timeout, ops)
             torch.cuda.empty_cache()
     if "host" in want:
         out["host"] = host_cost(xec, torch, args.step_timeout)
