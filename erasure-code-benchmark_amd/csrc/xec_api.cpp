@@ -1512,14 +1512,16 @@ xec_status xec_read_shards_device(const void* const* h_shards, size_t data_strid
 
 // ---- in-place block update -----------------------------------------------------
 // xec_update / xec_update_device: parity[c][i % m] ^= data[c][i] ^ new, then
-// data[c][i] = new, for the named blocks only (xec_kernels.hip, update).  The
+// data[c][i] = new, for the named blocks only: the ranged update's kernels over
+// [0, bs) without digests (xec_kernels.hip, update and ranged update).  The
 // delta keeps a class's syndrome, so xec_verify still flags a class that was
 // already corrupt; a re-encode would not.  Residency is uncapped (a lane has
 // 3-5 loads in flight, the table's 1-2 members): caps 1, 2, 4 and 8 were swept
 // once with one block per stripe at configs 2, 3 and 4 (tools/update_bench.py
-// --sweep, profiles/update/) -- caps 1 and 2 cost 1.4-2.6x everywhere, 4 is
-// 7-16 % slower, 8 equals none.  (With the parity store still sc1, cap 4 was
-// 3 % faster at config 3 and 7 % and 5 % slower at configs 2 and 4.)  The order
+// --sweep, profiles/update/; on the whole-block kernels these calls had then)
+// -- caps 1 and 2 cost 1.4-2.6x everywhere, 4 is 7-16 % slower, 8 equals none.
+// (With the parity store still sc1, cap 4 was 3 % faster at config 3 and 7 %
+// and 5 % slower at configs 2 and 4.)  The order
 // of the checks is: initialisation, xec_check_args, nothing to do, then the new
 // buffer and the list -- all on the host before any device call.
 static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
@@ -1536,6 +1538,40 @@ static xec_status update_check_new(const void* d_data, const void* d_parity, con
   return XEC_SUCCESS;
 }
 
+// What xec_update and xec_update_range do once their own argument checks have
+// passed: the scratch check of a list too long for the kernel arguments, the
+// capture rule, then the ranged kernels over the list by value or uploaded.
+// A whole-block update is the range [0, bs) without digests.
+static xec_status update_list_launch(void* d_data, void* d_parity, const void* d_new, size_t S,
+                                     size_t bs, size_t k, size_t m, const uint32_t* h_items,
+                                     size_t n, size_t offset, size_t len, uint64_t* d_digests,
+                                     void* d_scratch, size_t scratch_bytes, hipStream_t stream) {
+  const bool in_args = n <= xec::kArgItems;
+  if (!in_args) {
+    const xec_status st = check_scratch(d_scratch, scratch_bytes, xec_update_scratch_bytes(n));
+    if (st != XEC_SUCCESS) return st;
+  }
+  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (in_args) {
+    g_update_tiling_used = XEC_TILING_ARG_LIST;
+    return launch_status(__LINE__, xec::launch_update_range(
+                                       d_data, d_parity, d_new, nullptr, d_digests, g, ls,
+                                       xec::kUpdateArgListTiles, offset, len, stream, n, h_items));
+  }
+  return upload_list_and_launch(
+      n * 4, d_scratch, stream, __LINE__,
+      [&](uint32_t* staged) {
+        std::memcpy(staged, h_items, n * 4);
+        g_update_tiling_used = XEC_TILING_LIST;
+      },
+      [&] {
+        return xec::launch_update_range(d_data, d_parity, d_new, d_scratch, d_digests, g, ls,
+                                        xec::kUpdateListTiles, offset, len, stream, n);
+      });
+}
+
 static xec_status update_impl(void* d_data, void* d_parity, const void* d_new, size_t S,
                               size_t bs, size_t k, size_t m, const uint32_t* h_items,
                               size_t n, void* d_scratch, size_t scratch_bytes,
@@ -1548,30 +1584,8 @@ static xec_status update_impl(void* d_data, void* d_parity, const void* d_new, s
   st = update_check_new(d_data, d_parity, d_new, n * bs, S, bs, k, m);
   if (st != XEC_SUCCESS) return st;
   if (h_items == nullptr || !items_ascending(h_items, n, S, k)) return XEC_INVALID_COUNTS;
-  const bool in_args = n <= xec::kArgItems;
-  if (!in_args) {
-    st = check_scratch(d_scratch, scratch_bytes, xec_update_scratch_bytes(n));
-    if (st != XEC_SUCCESS) return st;
-  }
-  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
-  const xec::LaunchShape ls = launch_shape(bs, 0);
-  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
-  if (in_args) {
-    g_update_tiling_used = XEC_TILING_ARG_LIST;
-    return launch_status(__LINE__,
-                         xec::launch_update(d_data, d_parity, d_new, nullptr, g, ls,
-                                            xec::kUpdateArgListTiles, stream, n, h_items));
-  }
-  return upload_list_and_launch(
-      n * 4, d_scratch, stream, __LINE__,
-      [&](uint32_t* staged) {
-        std::memcpy(staged, h_items, n * 4);
-        g_update_tiling_used = XEC_TILING_LIST;
-      },
-      [&] {
-        return xec::launch_update(d_data, d_parity, d_new, d_scratch, g, ls,
-                                  xec::kUpdateListTiles, stream, n);
-      });
+  return update_list_launch(d_data, d_parity, d_new, S, bs, k, m, h_items, n, 0, bs, nullptr,
+                            d_scratch, scratch_bytes, stream);
 }
 
 xec_status xec_update(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
@@ -1604,8 +1618,8 @@ xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, si
   const xec::LaunchShape ls = launch_shape(bs, 0);
   const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
   g_update_tiling_used = XEC_TILING_CLASS;
-  return xec::launch_update(d_data, d_parity, d_new, d_mask, g, ls, xec::kUpdateClassTiles,
-                            stream) == hipSuccess
+  return xec::launch_update_range(d_data, d_parity, d_new, d_mask, nullptr, g, ls,
+                                  xec::kUpdateClassTiles, 0, bs, stream) == hipSuccess
              ? XEC_SUCCESS
              : XEC_DEVICE_ERROR;
 }
@@ -1997,9 +2011,9 @@ xec_status xec_readv_device(const void* d_data, const void* d_parity, size_t S, 
 // xec_update_range / xec_update_range_device: xec_update over bytes
 // [offset, offset + len) of each named block, and with d_digests the stored
 // digests of the touched data and parity blocks follow in the same pass
-// (xec_kernels.hip, ranged update).  Residency is uncapped, as the update
-// kernels: a lane has the same 3-5 loads in flight.  xec_digest_range_host is
-// the host's side of the upkeep identity.
+// (xec_kernels.hip, update and ranged update).  Residency is uncapped, as for
+// xec_update, which runs the same kernels.  xec_digest_range_host is the host's
+// side of the upkeep identity.
 uint64_t xec_digest_range_host(const void* bytes, size_t offset, size_t len) {
   const unsigned char* p = static_cast<const unsigned char*>(bytes);
   const uint64_t n0 = offset / 8;
@@ -2051,30 +2065,8 @@ static xec_status update_range_impl(void* d_data, void* d_parity, const void* d_
                           d_digests);
   if (st != XEC_SUCCESS) return st;
   if (!items_ascending(h_items, n, S, k)) return XEC_INVALID_COUNTS;
-  const bool in_args = n <= xec::kArgItems;
-  if (!in_args) {
-    st = check_scratch(d_scratch, scratch_bytes, xec_update_scratch_bytes(n));
-    if (st != XEC_SUCCESS) return st;
-  }
-  if (capturing(stream)) return DEVERR(hipSuccess);  // work to queue: see xec_decode
-  const xec::LaunchShape ls = launch_shape(bs, 0);
-  const xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
-  if (in_args) {
-    g_update_tiling_used = XEC_TILING_ARG_LIST;
-    return launch_status(__LINE__, xec::launch_update_range(
-                                       d_data, d_parity, d_new, nullptr, d_digests, g, ls,
-                                       xec::kUpdateArgListTiles, offset, len, stream, n, h_items));
-  }
-  return upload_list_and_launch(
-      n * 4, d_scratch, stream, __LINE__,
-      [&](uint32_t* staged) {
-        std::memcpy(staged, h_items, n * 4);
-        g_update_tiling_used = XEC_TILING_LIST;
-      },
-      [&] {
-        return xec::launch_update_range(d_data, d_parity, d_new, d_scratch, d_digests, g, ls,
-                                        xec::kUpdateListTiles, offset, len, stream, n);
-      });
+  return update_list_launch(d_data, d_parity, d_new, S, bs, k, m, h_items, n, offset, len,
+                            d_digests, d_scratch, scratch_bytes, stream);
 }
 
 xec_status xec_update_range(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,

@@ -181,21 +181,19 @@ constexpr int kRepairArgListTiles = 2;
 hipError_t launch_repair(void* d_data, void* d_parity, const uint8_t* d_bitmap,
                          const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
                          uint64_t n_items = 0, const uint32_t* h_items = nullptr);
-// Update tilings (xec_update, xec_update_device): data block i of stripe c takes
-// a new block and parity[c][i % m] ^= old ^ new; one tile folds every updated
-// member of its (stripe, class, chunk), so each parity granule has one writer.
-// Class: one tile per (stripe, class, chunk), d_sel = the S*k mask bytes
-// (nonzero = take the block), d_new mirrors d_data (any k, S).  List / ArgList:
-// one per (list position, chunk) over items c << 8 | i (i < k <= 256), strictly
-// ascending (the caller checked), d_new = the new blocks packed in list order;
-// d_sel = the n_items u32 items on the device (4-byte aligned), or h_items
-// passed by value (at most kArgItems).  No member-count template parameter.
+// Update tilings (launch_update_range, launch_write): data block i of stripe c
+// takes new bytes and parity[c][i % m] ^= old ^ new; one tile folds every
+// updated member of its (stripe, class, chunk), so each parity granule has one
+// writer.  Class: one tile per (stripe, class, chunk), d_sel = the S*k mask
+// bytes (nonzero = take the block), d_new mirrors d_data (any k, S).  List /
+// ArgList: one per (list position, chunk) over items c << 8 | i (i < k <= 256),
+// strictly ascending (the caller checked), d_new = the new bytes packed in list
+// order; d_sel = the n_items u32 items on the device (4-byte aligned), or
+// h_items passed by value (at most kArgItems).  No member-count template
+// parameter.
 constexpr int kUpdateClassTiles = 0;
 constexpr int kUpdateListTiles = 1;
 constexpr int kUpdateArgListTiles = 2;
-hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
-                         const Geometry& g, const LaunchShape& ls, int tiling, hipStream_t s,
-                         uint64_t n_items = 0, const uint32_t* h_items = nullptr);
 // Scrub (xec_verify): class tiles; d_flags[c*m + j] = 1 where the XOR of class
 // j's data blocks and its parity block is nonzero anywhere (the caller zeroes
 // d_flags first, stream-ordered).  Reads the batch, writes only those bytes.
@@ -292,11 +290,13 @@ hipError_t launch_readv_check(const uint8_t* d_bitmap, const uint32_t* d_iov, ui
                               int32_t* d_status, hipStream_t s);
 hipError_t launch_readv_scan(uint32_t* d_work, uint64_t n, uint64_t out_bytes, int32_t* d_status,
                              hipStream_t s);
-// Ranged update (xec_update_range, xec_update_range_device): launch_update over
-// bytes [offset, offset + len) of each named block only, tilings and d_sel /
-// h_items as there (kUpdate*Tiles); a tile is (list position or class, chunk of
-// the RANGE), chunks of 16*threads*unroll bytes.  List forms: item t's new
-// bytes are the len bytes at d_new + t*len; class form: d_new mirrors d_data.
+// Update and ranged update (xec_update, xec_update_device, xec_update_range,
+// xec_update_range_device): the delta fold over bytes [offset, offset + len) of
+// each named block only -- offset = 0, len = bs and no digests for the
+// whole-block calls -- with tilings and d_sel / h_items as kUpdate*Tiles
+// describes; a tile is (list position or class, chunk of the RANGE), chunks of
+// 16*threads*unroll bytes.  List forms: item t's new bytes are the len bytes at
+// d_new + t*len; class form: d_new mirrors d_data.
 // d_digests != nullptr (S*(k+m) u64, xec_digest's layout) adds
 // mix(new) - mix(old) over the range's words to the slot of every updated data
 // block and of the parity block of every class with an item, one 64-bit

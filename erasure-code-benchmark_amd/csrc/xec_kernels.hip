@@ -583,160 +583,6 @@ __global__ __launch_bounds__(T) void count_flags_kernel(const uint8_t* __restric
 }
 
 // ---------------------------------------------------------------------------
-// update (xec_update, xec_update_device): data block i of stripe c is replaced
-// by a new block and the class parity follows by the delta,
-//   parity[c][i % m] ^= data[c][i] ^ new;   data[c][i] = new
-// -- 3 block reads and 2 block writes per block, whatever k/m is.
-//
-// One writer per parity granule: a tile owns (stripe c, class j, column chunk)
-// for the whole call and folds EVERY updated member of that class,
-//   acc = parity;  per member: acc ^= old ^ new, data <- new;  parity <- acc
-// so there are no atomics, no memset pass and no LDS.  The loads in flight per
-// lane are 2 per member and the parity, independent of k/m: no NM parameter.
-//
-// In place: a lane stores the new data granule to the very address it loaded
-// the old one from, and the parity granule likewise; a granule belongs to one
-// lane of one tile, so program order within the lane is all that is relied on.
-// The new data block is stored sc1, as decode stores a rebuilt block.  The
-// parity block is stored nt, as encode stores parity: both were started from
-// sc1, and against that a build with nt here measured 15.7 % faster at config
-// 3 (185.8 against 220.4 us for one block per stripe, encode's spread
-// 1.4-2.0 %), 6.8 % at config 4 and equal at config 2 (tools/update_bench.py,
-// DESIGN.md §3 *Update*, profiles/update/parity_store_*.json).
-// ---------------------------------------------------------------------------
-constexpr int kUpdateDataStoreAux = 16;   // sc1
-constexpr int kUpdateParityStoreAux = 2;  // nt
-
-// This lane's U granules of one block at `off` (granule u at off + u*T*16,
-// taking part only while inside the block: ragged tiles).
-template <int U, bool NT, int T>
-__device__ __forceinline__ void load_granules(u32x4 (&v)[U], const uint8_t* block, uint64_t off,
-                                              uint64_t bs) {
-  constexpr uint64_t kStep = (uint64_t)T * 16;
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (off + u * kStep < bs) v[u] = ld16<NT>(block + off + u * kStep);
-}
-
-template <int U, bool NT, int T, int SAUX>
-__device__ __forceinline__ void store_granules(const u32x4 (&v)[U], uint8_t* block, uint64_t off,
-                                               uint64_t bs) {
-  constexpr uint64_t kStep = (uint64_t)T * 16;
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (off + u * kStep < bs) st16_block<NT, SAUX>(block, off + u * kStep, v[u]);
-}
-
-// acc ^= old ^ new over this lane's granules of one data block; the block
-// takes the new bytes.
-template <int U, bool NT, int T>
-__device__ __forceinline__ void fold_member(u32x4 (&acc)[U], uint8_t* block, const uint8_t* fresh,
-                                            uint64_t off, uint64_t bs) {
-  constexpr uint64_t kStep = (uint64_t)T * 16;
-  u32x4 o[U], n[U];
-  load_granules<U, NT, T>(o, block, off, bs);
-  load_granules<U, NT, T>(n, fresh, off, bs);
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (off + u * kStep < bs) acc[u] ^= o[u] ^ n[u];
-  store_granules<U, NT, T, kUpdateDataStoreAux>(n, block, off, bs);
-}
-
-// Work-list tiles: one per (list position e, column chunk); item e is
-// c << 8 | i (i < k) and its new block is the e-th of d_new.  The host checked
-// the list strictly ascending, so a stripe's items are adjacent: tile e owns
-// its class's parity chunk iff no earlier item of its stripe is of the same
-// class, and then folds every later one of that class too; otherwise it has
-// nothing to do.  `at(q)` reads item q with a scalar load.
-template <int U, bool NT, int T, typename At>
-__device__ __forceinline__ void update_list_tile(uint8_t* data, uint8_t* parity,
-                                                 const uint8_t* __restrict__ fresh, uint64_t e,
-                                                 uint64_t n, uint64_t chunk, const Geometry& g,
-                                                 At at) {
-  const uint32_t m = (uint32_t)g.m;
-  const uint32_t item = at(e);
-  const uint32_t c = item >> 8, j = (item & 0xFFu) % m;
-  for (uint64_t q = e; q > 0;) {
-    const uint32_t prev = at(--q);
-    if ((prev >> 8) != c) break;
-    if ((prev & 0xFFu) % m == j) return;  // an earlier item's tile folds this one
-  }
-  const uint64_t off = (rotated(chunk, c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
-  uint8_t* par = parity + ((uint64_t)c * g.m + j) * g.bs;
-  u32x4 acc[U];
-  load_granules<U, NT, T>(acc, par, off, g.bs);
-  uint32_t it = item;
-  for (uint64_t q = e;;) {
-    const uint32_t i = it & 0xFFu;
-    if (i % m == j)
-      fold_member<U, NT, T>(acc, data + ((uint64_t)c * g.k + i) * g.bs, fresh + q * g.bs, off,
-                            g.bs);
-    if (++q == n) break;
-    it = at(q);
-    if ((it >> 8) != c) break;
-  }
-  store_granules<U, NT, T, kUpdateParityStoreAux>(acc, par, off, g.bs);
-}
-
-template <int U, bool NT, int T>
-__global__ __launch_bounds__(T) void update_list_kernel(uint8_t* data, uint8_t* parity,
-                                                        const uint8_t* __restrict__ fresh,
-                                                        const uint32_t* __restrict__ items,
-                                                        Geometry g) {
-  const uint64_t n = g.total_tiles / g.tiles_per_block;
-  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
-    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as decode_list_kernel
-    update_list_tile<U, NT, T>(data, parity, fresh, t / g.tiles_per_block, n,
-                               t % g.tiles_per_block, g,
-                               [&](uint64_t q) { return *(const_u32_as4)(items + q); });
-  }
-}
-
-template <int U, bool NT, int T, uint32_t CAP>
-__global__ __launch_bounds__(T) void update_arglist_kernel(uint8_t* data, uint8_t* parity,
-                                                           const uint8_t* __restrict__ fresh,
-                                                           Geometry g, ArgItems<CAP> items) {
-  const uint64_t n = g.total_tiles / g.tiles_per_block;
-  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
-    const uint64_t t = g.total_tiles - 1 - t0;
-    update_list_tile<U, NT, T>(data, parity, fresh, t / g.tiles_per_block, n,
-                               t % g.tiles_per_block, g,
-                               [&](uint64_t q) { return items.v[q]; });
-  }
-}
-
-// Class tiles over a device mask (xec_update_device): mask[c*k + i] != 0 means
-// "take block i of stripe c from the shadow buffer", which mirrors data's
-// layout.  The tile scans its class's k/m mask bytes (scalar dword loads, as
-// repair_class_kernel) and folds the marked members; a class with none reads
-// and writes nothing.
-template <int U, bool NT, int T>
-__global__ __launch_bounds__(T) void update_class_kernel(uint8_t* data, uint8_t* parity,
-                                                         const uint8_t* __restrict__ fresh,
-                                                         const uint8_t* __restrict__ mask,
-                                                         Geometry g) {
-  const uint32_t nm = (uint32_t)g.nm;
-  const uint64_t stride = g.m * g.bs;
-  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
-    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as encode
-    const TileCoord tc = tile_coord(t, g);
-    const uint64_t row = reinterpret_cast<uint64_t>(mask + tc.c * g.k) + tc.j;
-    const uint64_t first = (tc.c * g.k + tc.j) * g.bs;
-    const uint64_t off = (rotated(tc.chunk, tc.c, g) * (uint64_t)(T * U) + threadIdx.x) * 16;
-    uint8_t* par = parity + (tc.c * g.m + tc.j) * g.bs;
-    u32x4 acc[U];
-    bool any = false;
-    for (uint32_t r = 0; r < nm; ++r) {
-      if (sbyte(row + (uint64_t)r * g.m) == 0) continue;
-      if (!any) load_granules<U, NT, T>(acc, par, off, g.bs);
-      any = true;
-      fold_member<U, NT, T>(acc, data + first + r * stride, fresh + first + r * stride, off, g.bs);
-    }
-    if (any) store_granules<U, NT, T, kUpdateParityStoreAux>(acc, par, off, g.bs);
-  }
-}
-
-// ---------------------------------------------------------------------------
 // check + list (xec_decode_device_list): one thread per (stripe, class), as
 // check_kernel, and a class that lost exactly one block, a data block, appends
 // its work item (c << 8 | i, xec_internal.h) after the list header.  A wave
@@ -1060,47 +906,6 @@ hipError_t launch_count_flags(const uint8_t* d_flags, uint64_t n, uint32_t* d_co
   if (n == 0) return hipSuccess;
   const uint32_t grid = grid_for((n + 255) / 256, 1024, 256);
   return launch(count_flags_kernel<256>, grid, 256, 0, s, d_flags, n, d_count);
-}
-
-// ---- update launcher -------------------------------------------------------
-hipError_t launch_update(void* d_data, void* d_parity, const void* d_new, const void* d_sel,
-                         const Geometry& g_class, const LaunchShape& ls, int tiling,
-                         hipStream_t s, uint64_t n_items, const uint32_t* h_items) {
-  // class tiles (stripe, class, chunk) over the device mask d_sel:
-  // update_class_kernel; list tiles (list position, chunk): update_list_kernel
-  // over the n_items entries d_sel holds, or update_arglist_kernel over h_items
-  // passed by value
-  Geometry g = g_class;
-  if (tiling == kUpdateListTiles || tiling == kUpdateArgListTiles)
-    g.total_tiles = n_items * g.tiles_per_block;
-  if (g.total_tiles == 0) return hipSuccess;
-  if (g.k > 256 && tiling != kUpdateClassTiles) return hipErrorInvalidValue;
-  if (tiling == kUpdateArgListTiles && (n_items > kArgItems || h_items == nullptr))
-    return hipErrorInvalidValue;
-  if (tiling != kUpdateArgListTiles && d_sel == nullptr) return hipErrorInvalidValue;
-  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
-  const uint32_t lds = ls.lds_bytes;
-  uint8_t* dd = static_cast<uint8_t*>(d_data);
-  uint8_t* pp = static_cast<uint8_t*>(d_parity);
-  const uint8_t* ff = static_cast<const uint8_t*>(d_new);
-  return with_shape(ls.unroll, ls.nt, ls.threads, [&](auto sh) {
-    constexpr int U = decltype(sh)::U, T = decltype(sh)::T;
-    constexpr bool NT = decltype(sh)::NT;
-    switch (tiling) {
-      case kUpdateArgListTiles:
-        return with_capacity(n_items, [&](auto cap) {
-          constexpr uint32_t CAP = decltype(cap)::value;
-          return launch_codec(update_arglist_kernel<U, NT, T, CAP>, grid, T, lds, s, dd, pp, ff, g,
-                              arg_items<CAP>(h_items, n_items));
-        });
-      case kUpdateListTiles:
-        return launch_codec(update_list_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
-                            static_cast<const uint32_t*>(d_sel), g);
-      default:
-        return launch_codec(update_class_kernel<U, NT, T>, grid, T, lds, s, dd, pp, ff,
-                            static_cast<const uint8_t*>(d_sel), g);
-    }
-  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1868,20 +1673,46 @@ hipError_t launch_readv_scan(uint32_t* d_work, uint64_t n, uint64_t out_bytes, i
 }
 
 // ---------------------------------------------------------------------------
-// ranged update (xec_update_range, xec_update_range_device).  Kernels and
-// launchers together.
+// update and ranged update (xec_update, xec_update_device, xec_update_range,
+// xec_update_range_device).  Kernels and launcher together.
 //
-// The update above over bytes [offset, offset + len) of each named block only,
+// update: data block i of stripe c is replaced by a new block and the class
+// parity follows by the delta,
+//   parity[c][i % m] ^= data[c][i] ^ new;   data[c][i] = new
+// -- 3 block reads and 2 block writes per block, whatever k/m is.
+//
+// One writer per parity granule: a tile owns (stripe c, class j, column chunk)
+// for the whole call and folds EVERY updated member of that class,
+//   acc = parity;  per member: acc ^= old ^ new, data <- new;  parity <- acc
+// so there are no atomics, no memset pass and no LDS.  The loads in flight per
+// lane are 2 per member and the parity, independent of k/m: no NM parameter.
+//
+// In place: a lane stores the new data granule to the very address it loaded
+// the old one from, and the parity granule likewise; a granule belongs to one
+// lane of one tile, so program order within the lane is all that is relied on.
+// The new data block is stored sc1, as decode stores a rebuilt block.  The
+// parity block is stored nt, as encode stores parity: both were started from
+// sc1, and against that a build with nt here measured 15.7 % faster at config
+// 3 (185.8 against 220.4 us for one block per stripe, encode's spread
+// 1.4-2.0 %), 6.8 % at config 4 and equal at config 2 (tools/update_bench.py,
+// DESIGN.md §3 *Update*, profiles/update/parity_store_*.json; taken on the
+// whole-block kernels these replaced, which stored the same way).
+//
+// ranged update: the same over bytes [offset, offset + len) of each named
+// block only,
 //   parity[c][i % m][range] ^= data[c][i][range] ^ new;   data[c][i][range] = new
 // with the read's range addressing: a tile is (list position or class, chunk
 // of the RANGE), chunk q covers block offsets offset + q*16*T*U onwards and
 // g.tiles_per_block counts the chunks of the range.  A lane's granule is never
-// formed below `offset` and takes part only while below offset + len.
-// Ownership is update's: the first item of a class in its stripe owns that
-// class's parity chunk and folds the later ones, one lane owns a granule, and
-// both stores go in place through st16_block (data sc1, parity nt).  These are
-// update_list_tile / fold_member written again, not shared with them: the old
-// kernels stay instruction for instruction what they were.
+// formed below `offset` and takes part only while below offset + len.  The
+// first item of a class in its stripe owns that class's parity chunk and folds
+// the later ones, one lane owns a granule, and both stores go in place through
+// st16_block (data sc1, parity nt).  There is no column rotation.
+//
+// The whole-block entry points run these kernels with offset = 0, len = bs and
+// no digests (DIG = false): the tiles are then make_geometry's, and item e's
+// new block is at fresh + e*bs.  They had kernels of their own once, the same
+// fold without a range; DESIGN.md §3 *Update* records the comparison.
 //
 // New bytes.  List forms: item e's len bytes are packed at fresh + e*len, so a
 // granule at block offset o is read from fresh + e*len + (o - offset).  Class
@@ -1903,8 +1734,8 @@ hipError_t launch_readv_scan(uint32_t* d_work, uint64_t n, uint64_t out_bytes, i
 // matter.  DIG = false is a separate instantiation with no multiply and no
 // atomic in it.
 // ---------------------------------------------------------------------------
-constexpr int kPatchDataStoreAux = 16;   // sc1, as update
-constexpr int kPatchParityStoreAux = 2;  // nt, as update
+constexpr int kPatchDataStoreAux = 16;   // sc1
+constexpr int kPatchParityStoreAux = 2;  // nt
 
 // One wave's sum of x goes to *slot.  Called from wave-uniform control flow.
 __device__ __forceinline__ void patch_wave_add(uint64_t* slot, uint64_t x) {
@@ -1953,8 +1784,12 @@ __device__ __forceinline__ uint64_t patch_fold(u32x4 (&acc)[U], uint8_t* block, 
   return d;
 }
 
-// List tiles: one per (list position e, chunk of the range), ownership as
-// update_list_tile.
+// List tiles: one per (list position e, chunk of the range); item e is
+// c << 8 | i (i < k).  The host checked the list strictly ascending, so a
+// stripe's items are adjacent: tile e owns its class's parity chunk iff no
+// earlier item of its stripe is of the same class, and then folds every later
+// one of that class too; otherwise it has nothing to do.  `at(q)` reads item q
+// with a scalar load.
 template <int U, bool NT, int T, bool DIG, typename At>
 __device__ __forceinline__ void patch_list_tile(uint8_t* data, uint8_t* parity,
                                                 const uint8_t* __restrict__ fresh,
@@ -2009,7 +1844,7 @@ __global__ __launch_bounds__(T) void patch_list_kernel(uint8_t* data, uint8_t* p
                                                        Geometry g) {
   const uint64_t n = g.total_tiles / g.tiles_per_block;
   for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
-    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as update_list_kernel
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as decode_list_kernel
     patch_list_tile<U, NT, T, DIG>(data, parity, fresh, digests, t / g.tiles_per_block, n,
                                    t % g.tiles_per_block, rr, g,
                                    [&](uint64_t q) { return *(const_u32_as4)(items + q); });
@@ -2030,8 +1865,11 @@ __global__ __launch_bounds__(T) void patch_arglist_kernel(uint8_t* data, uint8_t
   }
 }
 
-// Class tiles over a device mask (xec_update_range_device), as
-// update_class_kernel: (stripe, class, chunk of the range); fresh mirrors data.
+// Class tiles over a device mask (xec_update_device, xec_update_range_device):
+// (stripe, class, chunk of the range); mask[c*k + i] != 0 means "take block i
+// of stripe c from the shadow buffer", which mirrors data's layout.  The tile
+// scans its class's k/m mask bytes (scalar dword loads, as repair_class_kernel)
+// and folds the marked members; a class with none reads and writes nothing.
 template <int U, bool NT, int T, bool DIG>
 __global__ __launch_bounds__(T) void patch_class_kernel(uint8_t* data, uint8_t* parity,
                                                         const uint8_t* __restrict__ fresh,
@@ -2043,7 +1881,7 @@ __global__ __launch_bounds__(T) void patch_class_kernel(uint8_t* data, uint8_t* 
   const uint64_t stride = g.m * g.bs;
   const uint64_t end = rr.offset + rr.len;
   for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
-    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as update_class_kernel
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the batch, as encode
     const TileCoord tc = tile_coord(t, g);
     const uint64_t mrow = reinterpret_cast<uint64_t>(mask + tc.c * g.k) + tc.j;
     const uint64_t first = (tc.c * g.k + tc.j) * g.bs;

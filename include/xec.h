@@ -503,7 +503,10 @@ int xec_shards_arg_capacity_used(void);
  * (XEC_INVALID_ALIGNMENT), not NULL and of at least
  * xec_update_scratch_bytes(n_items) bytes (XEC_INVALID_SIZE).  Not capturable,
  * as xec_repair: on a capturing stream a call with work returns
- * XEC_DEVICE_ERROR with nothing queued. */
+ * XEC_DEVICE_ERROR with nothing queued.
+ * Once its own checks above have passed, the call runs the kernels of
+ * xec_update_range over offset = 0, len = bs without digests; of xec_set_launch
+ * all four arguments apply, xec_set_rotation does not. */
 xec_status xec_update(void* d_data, void* d_parity, const void* d_new, size_t S, size_t bs,
                       size_t k, size_t m, const uint32_t* h_items, size_t n_items,
                       void* d_scratch, size_t scratch_bytes, hipStream_t stream);
@@ -524,7 +527,8 @@ size_t xec_update_scratch_bytes(size_t n_items);
  * XEC_INVALID_SIZE; d_new's alignment and overlap (over S*k*bs bytes),
  * xec_check_args and initialisation as xec_update; nothing is queued when an
  * argument is rejected.  Bytes identical to xec_update's with the same set of
- * blocks. */
+ * blocks.  The kernel is xec_update_range_device's over offset = 0, len = bs
+ * without digests; xec_set_rotation does not apply. */
 xec_status xec_update_device(void* d_data, void* d_parity, const void* d_new, size_t S,
                              size_t bs, size_t k, size_t m, const uint8_t* d_mask,
                              hipStream_t stream);
@@ -1170,9 +1174,13 @@ xec_status xec_set_validate_kernel(int mode);
  * so results are identical; it changes which columns of the stripes in flight
  * together are read at once.  0 = automatic (the measured default), -1 = none,
  * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
- * It does not apply to xec_read / xec_read_device, xec_readv / xec_readv_device, xec_update_range /
- * xec_update_range_device and xec_write / xec_write_device: their tiles walk the chunks of each item's byte
- * range, not a column of every stripe. */
+ * It does not apply to xec_read / xec_read_device, xec_readv / xec_readv_device,
+ * xec_update / xec_update_device, xec_update_range / xec_update_range_device
+ * and xec_write / xec_write_device: their tiles walk the chunks of each item's
+ * byte range, not a column of every stripe.  (xec_update and xec_update_device
+ * applied an explicit rotation while they had kernels of their own; the
+ * automatic setting was none for them, so only a caller that set one sees the
+ * order of a block's chunks change, never a byte of the result.) */
 xec_status xec_set_rotation(int tiles);
 
 /* The calling thread's overrides above as one value.  A caller that fans its

@@ -215,6 +215,85 @@ def test_list_capacities_host_form(gpu, oracle, n):
         c.restore()
 
 
+def run_whole_range(xec, c: Case, blocks, fresh, entry):
+    """run_update's call through the ranged entry points: [0, bs), no digests."""
+    torch = _torch()
+    S, k, m, bs = c.S, c.k, c.m, c.bs
+    n = len(blocks)
+    if entry == "host":
+        new = torch.full(((n + 2) * bs,), 0xA5, dtype=torch.uint8, device="cuda")
+        new[: n * bs] = torch.from_numpy(np.ascontiguousarray(fresh).reshape(-1)).to("cuda")
+        scratch = torch.empty(max(xec.update_scratch_bytes(n), 4), dtype=torch.uint8, device="cuda")
+        st = xec.update_range(c.d, c.p, new, S, bs, k, m, items_of(blocks), n, 0, bs, None,
+                              scratch, scratch.numel(), c.b.stream)
+    else:
+        h_shadow = np.full((S, k, bs), 0xA5, np.uint8)
+        mask = np.zeros((S, k), np.uint8)
+        for t, (cs, i) in enumerate(blocks):
+            h_shadow[cs, i] = fresh[t]
+            mask[cs, i] = (1, 2, 255)[t % 3]
+        st = xec.update_range_device(c.d, c.p, torch.from_numpy(h_shadow.reshape(-1)).to("cuda"),
+                                     S, bs, k, m, torch.from_numpy(mask.reshape(-1)).to("cuda"),
+                                     0, bs, None, c.b.stream)
+    torch.cuda.synchronize()
+    return st
+
+
+@pytest.mark.parametrize("bs", [256, 1280])
+@pytest.mark.parametrize("k,m", [(2, 1), (4, 2)])
+def test_whole_block_update_is_the_ranged_update(gpu, oracle, k, m, bs):
+    """xec_update against xec_update_range(offset=0, len=bs, d_digests=NULL) and
+    xec_update_device against xec_update_range_device, on identical inputs:
+    byte-identical data and parity, both equal to the oracle's re-encode, and
+    the same tiling reported.
+
+    Shapes: the ABI takes block sizes that are multiples of 256 only, so the
+    smallest block (256: a quarter of the default one-wave tile, 48 of its 64
+    lanes idle) stands for "one granule", and 1280 (one full default tile and a
+    ragged second one of 256 bytes) for "a tile plus 16 bytes"; 16 and 1040
+    themselves must be refused alike by all four calls.  Lists at S = 3: two
+    items of one class in one stripe (the owner folds the later one) with an
+    item of another stripe, and an item in the last stripe only; at S = 520 a
+    list of 1,030 items, which is uploaded (tiling 3) where the others travel in
+    the kernel arguments (tiling 4)."""
+    torch = _torch()
+    St = gpu.Status
+    rng = np.random.default_rng(100 * k + bs)
+    long_S = 520
+    every = [(cs, i) for cs in range(long_S) for i in range(k)]
+    long_list = sorted(every[q] for q in rng.permutation(len(every))[:1030])
+    for S, blocks in [(3, [(0, k - 1), (1, 0), (1, m)]), (3, [(2, 1)]), (long_S, long_list)]:
+        c = Case.get(gpu, oracle, S, k, m, bs)
+        fresh = rng.integers(0, 256, size=(len(blocks), bs), dtype=np.uint8)
+        exp_d, exp_p = expected(oracle, c, c.ref_d.cpu().numpy(), blocks, fresh)
+        try:
+            for entry in ENTRIES:
+                tiling = 2 if entry == "device" else 4 if len(blocks) <= 1024 else 3
+                assert run_update(gpu, c, blocks, fresh, entry) == St.SUCCESS
+                assert gpu.update_tiling_used() == tiling
+                assert_state(c, exp_d, exp_p, f"after {entry} update of {len(blocks)} at S={S}")
+                d_whole, p_whole = c.d.clone(), c.p.clone()
+                c.restore()
+                assert run_whole_range(gpu, c, blocks, fresh, entry) == St.SUCCESS
+                assert gpu.update_tiling_used() == tiling
+                assert torch.equal(c.d, d_whole) and torch.equal(c.p, p_whole), (entry, S)
+                assert_state(c, exp_d, exp_p, f"after {entry} ranged update over [0, bs) at S={S}")
+                c.restore()
+        finally:
+            c.restore()
+    # block sizes below the ABI's granularity: every form refuses them, nothing changes
+    c = Case.get(gpu, oracle, 3, k, m, bs)
+    items, s = items_of([(2, 1)]), c.b.stream
+    for bad in (16, 1040):
+        assert gpu.update(c.d, c.p, c.ref_d, 3, bad, k, m, items, 1, None, 0, s) == St.INVALID_SIZE
+        assert gpu.update_range(c.d, c.p, c.ref_d, 3, bad, k, m, items, 1, 0, bad, None, None, 0,
+                                s) == St.INVALID_SIZE
+        assert gpu.update_device(c.d, c.p, c.ref_d, 3, bad, k, m, c.ref_d, s) == St.INVALID_SIZE
+        assert gpu.update_range_device(c.d, c.p, c.ref_d, 3, bad, k, m, c.ref_d, 0, bad, None,
+                                       s) == St.INVALID_SIZE
+    c.assert_exact("after refused block sizes")
+
+
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_update_keeps_the_syndrome(gpu, oracle, entry):
     """A class that was corrupt before the update is still flagged after it (a

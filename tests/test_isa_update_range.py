@@ -1,5 +1,6 @@
-"""ISA-level invariants of the ranged-update kernels (CPU only: hipcc
-cross-compiles; the listing is `make asm`'s, as tests/test_isa_update.py reads
+"""ISA-level invariants of the ranged-update kernels, which xec_update and
+xec_update_device run too, over [0, bs) with DIG=false (CPU only: hipcc
+cross-compiles; the listing is `make asm`'s, as tests/test_isa_repair.py reads
 it).
 
 * the kernels are templated <U, NT, T, DIG>: 2 unrolls x 2 policies x 2

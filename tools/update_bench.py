@@ -19,7 +19,8 @@ is not a difference.
      stripe in 9 written and every stripe written;
   D  (--sweep) A's update under residency caps 1, 2, 4, 8 and the shipped
      choice.  The parity store's policy is a constant of the kernel source
-     (kUpdateParityStoreAux, csrc/xec_kernels.hip): to compare another value,
+     (kPatchParityStoreAux, csrc/xec_kernels.hip: xec_update runs the ranged
+     update's kernels over whole blocks): to compare another value,
      run part A once more with XEC_LIB naming a library built with it and
      compare the two runs' ratios to encode.
 

@@ -17,8 +17,12 @@ difference inside that spread is not a difference.
   W  whole blocks with upkeep, one block per stripe at configs 2, 3 and 4:
      xec_update_range(0, bs, digests) against xec_update + xec_digest(select),
      the two-pass path;
-  N  whole blocks without upkeep at the same configs: xec_update_range(0, bs)
-     against xec_update -- the same bytes through the new tile.
+  N  a sanity row, not a comparison: whole blocks without upkeep at the same
+     configs, xec_update_range(0, bs) against xec_update.  Both calls run the
+     same kernel (xec_update is the ranged update over [0, bs) without
+     digests), so the row shows what two runs of one kernel differ by here.
+     It compared two kernels while xec_update had its own (DESIGN.md §3
+     *Ranged update*, item 3).
 
 The two-pass figure is the sum of the two calls' kernel times, each from its
 own dispatch; the small kernel with which xec_digest zeroes the selected slots
@@ -203,7 +207,8 @@ def main():
             if "N" in parts:
                 out["rows"].append(compare(
                     sh, [("update", "update"), ("update_range", "range")],
-                    us, args.rounds, args.iters, lim, f"N {name} whole blocks without upkeep"))
+                    us, args.rounds, args.iters, lim,
+                    f"N {name} whole blocks without upkeep (sanity: one kernel twice)"))
             del us
         del sh
         torch.cuda.empty_cache()
