@@ -2197,6 +2197,119 @@ xec_status xec_write_device(void* d_data, void* d_parity, const void* d_new, siz
   return le == hipSuccess ? XEC_SUCCESS : DEVERR(le);
 }
 
+// ---- shard-major degraded write and vectored read ---------------------------------------
+// xec_write_shards_device / xec_readv_shards_device: the list-tiled degraded
+// write with its list checked on the device, and xec_readv_device, both over a
+// shard table (xec_kernels.hip).  Launch shape and residency are the batch
+// calls' (uncapped for the write; read_occupancy for the read), swept on the
+// batch layout only.  Neither touches xec_write_tiling_used or
+// xec_readv_tiling_used, as xec_read_shards_device leaves xec_read_tiling_used.
+xec_status xec_write_shards_device(const void* const* h_shards, size_t data_stride,
+                                   size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                   const uint8_t* d_bitmap, const uint32_t* d_items,
+                                   size_t n_items, size_t offset, size_t len, const void* d_new,
+                                   uint64_t* d_digests, int32_t* d_status, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (n_items == 0 || S == 0)
+    return hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) == hipSuccess ? XEC_SUCCESS
+                                                                              : XEC_DEVICE_ERROR;
+  if (k + m > kRepairItemMaxRow || S > kWorkItemMaxStripes) return XEC_INVALID_SIZE;
+  if (len == 0 || offset % 16 != 0 || len % 16 != 0 || offset > bs || len > bs - offset)
+    return XEC_INVALID_SIZE;
+  if (d_new == nullptr || d_items == nullptr) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_new) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(d_items) % 4 != 0 ||
+      reinterpret_cast<uintptr_t>(d_digests) % 8 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  // the tile count is at most n_items * len / 16, so it fits once n_items * len does
+  if (n_items > SIZE_MAX / len) return XEC_INVALID_SIZE;
+  st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  const size_t new_bytes = n_items * len, dig_bytes = d_digests ? 8 * S * (k + m) : 0;
+  if (overlaps_a_shard_hull(d_new, new_bytes, h_shards, data_stride, parity_stride, S, bs, k, m) ||
+      overlaps_a_shard_hull(d_digests, dig_bytes, h_shards, data_stride, parity_stride, S, bs, k,
+                            m) ||
+      ranges_overlap(d_new, new_bytes, d_digests, dig_bytes))
+    return XEC_INVALID_SIZE;
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  const xec::LaunchShape ls = launch_shape(bs, 0);
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  if (xec::launch_write_items_check(d_bitmap, d_items, n_items, g, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  const hipError_t le =
+      xec::launch_write_shards(h_shards, data_stride, parity_stride, d_new, d_items, d_bitmap,
+                               d_digests, g, ls, offset, len, n_items, stream);
+  if (le != hipSuccess) return DEVERR(le);
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
+xec_status xec_readv_shards_device(const void* const* h_shards, size_t data_stride,
+                                   size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                   const uint8_t* d_bitmap, const xec_iov* d_iov, size_t n_items,
+                                   void* d_out, size_t out_bytes, void* d_work, size_t work_bytes,
+                                   int32_t* d_status, hipStream_t stream) {
+  const KernelEventsScope events_scope;
+  g_shards_cap_used = 0;
+  if (!g_initialised.load(std::memory_order_acquire)) return XEC_NOT_INITIALIZED;
+  xec_status st = xec_check_args(nullptr, nullptr, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  // every argument is checked before any work is queued on the stream
+  if (d_status == nullptr || reinterpret_cast<uintptr_t>(d_status) % 4 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  if (n_items == 0 || S == 0)
+    return hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) == hipSuccess ? XEC_SUCCESS
+                                                                              : XEC_DEVICE_ERROR;
+  st = readv_check_batch(S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (d_out == nullptr || d_iov == nullptr || d_work == nullptr) return XEC_INVALID_SIZE;
+  if (work_bytes < xec_readv_device_work_bytes(n_items)) return XEC_INVALID_SIZE;
+  if (reinterpret_cast<uintptr_t>(d_out) % 16 != 0 || reinterpret_cast<uintptr_t>(d_iov) % 4 != 0 ||
+      reinterpret_cast<uintptr_t>(d_work) % 8 != 0)
+    return XEC_INVALID_ALIGNMENT;
+  st = check_shard_table(h_shards, data_stride, parity_stride, S, bs, k, m);
+  if (st != XEC_SUCCESS) return st;
+  if (overlaps_a_shard_hull(d_out, out_bytes, h_shards, data_stride, parity_stride, S, bs, k, m))
+    return XEC_INVALID_SIZE;
+  // the most tiles an entry can have is at the smallest tile, 1 KiB
+  if ((uint64_t)n_items > 0xFFFFFFFFull / (((uint64_t)bs + 1023) / 1024)) return XEC_INVALID_SIZE;
+  const StreamDevice sd(stream);
+  if (!sd.ok()) return XEC_DEVICE_ERROR;
+  xec::LaunchShape ls = launch_shape(bs, read_occupancy(k / m, d_bitmap ? 1 : 0));
+  xec::Geometry g = xec::make_geometry(S, bs, k, m, ls);
+  // the grid bound of xec_readv_device
+  const uint64_t tile_bytes = 16ull * (uint64_t)ls.threads * (uint64_t)ls.unroll;
+  const uint64_t bound = (uint64_t)out_bytes / tile_bytes + n_items;
+  if (ls.max_grid == 0) {
+    const uint64_t resident = resident_workgroups(ls);
+    if (resident == 0) return XEC_DEVICE_ERROR;
+    const uint64_t want = bound / 8 < kDevListMaxGrid ? bound / 8 : kDevListMaxGrid;
+    ls.max_grid = (uint32_t)(want > resident ? want : resident);
+  }
+  if (hipMemsetAsync(d_status, 0, sizeof(int32_t), stream) != hipSuccess) return XEC_DEVICE_ERROR;
+  uint32_t* work = static_cast<uint32_t*>(d_work);
+  const uint32_t* iov = reinterpret_cast<const uint32_t*>(d_iov);
+  if (xec::launch_readv_check(d_bitmap, iov, n_items, g, tile_bytes, work, d_status, stream) !=
+          hipSuccess ||
+      xec::launch_readv_scan(work, n_items, out_bytes, d_status, stream) != hipSuccess)
+    return XEC_DEVICE_ERROR;
+  g.gate = d_status;
+  const hipError_t le =
+      xec::launch_readv_shards(h_shards, data_stride, parity_stride, d_out, g, ls, n_items, bound,
+                               iov, d_bitmap, work, stream);
+  if (le != hipSuccess) return DEVERR(le);
+  g_shards_cap_used = (int)xec::shard_tab_capacity(k + m);
+  return XEC_SUCCESS;
+}
+
 xec_status xec_erase(void* d_data, void* d_parity, size_t S, size_t bs, size_t k, size_t m,
                      const uint8_t* d_bitmap, hipStream_t stream) {
   xec_status st = check_entry(d_data, d_parity, bs, k, m);

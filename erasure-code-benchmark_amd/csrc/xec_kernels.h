@@ -371,6 +371,30 @@ hipError_t launch_read_shards(const void* const* h_shards, uint64_t dstride, uin
                               void* d_out, const Geometry& g, const LaunchShape& ls,
                               uint64_t offset, uint64_t len, uint64_t n_items,
                               const uint32_t* d_items, const uint8_t* d_bitmap, hipStream_t s);
+// Shard-major degraded write (xec_write_shards_device): launch_write's list
+// tiles over a shard table with list and bitmap on the device.  d_items = n_items
+// u32 items c << 8 | i, d_new = their new bytes packed in list order, d_bitmap
+// the batch bitmap or nullptr (everything present), d_digests as launch_write;
+// the owning tile reads its class's two loss bytes from the bitmap.  g.gate
+// must be set to the verdict of launch_write_items_check, which leaves
+// *d_status = max over the items of 0, 3 (c >= S, i >= k, or not above its
+// predecessor) and 4 (lost with another block of its class lost); the caller
+// zeroes *d_status first, stream-ordered.  The check runs with d_bitmap ==
+// nullptr too (the order rule).  No cap on n_items.
+hipError_t launch_write_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                               const void* d_new, const uint32_t* d_items,
+                               const uint8_t* d_bitmap, uint64_t* d_digests, const Geometry& g,
+                               const LaunchShape& ls, uint64_t offset, uint64_t len,
+                               uint64_t n_items, hipStream_t s);
+hipError_t launch_write_items_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
+                                    const Geometry& g, int32_t* d_status, hipStream_t s);
+// launch_readv with kReadDevTiles over a shard table: d_iov, d_bitmap, d_work,
+// n, tiles and g.gate as there (launch_readv_check and launch_readv_scan touch
+// no block and serve both layouts).
+hipError_t launch_readv_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                               void* d_out, const Geometry& g, const LaunchShape& ls, uint64_t n,
+                               uint64_t tiles, const uint32_t* d_iov, const uint8_t* d_bitmap,
+                               const uint32_t* d_work, hipStream_t s);
 // Device-side recoverability check (xorec_utils.hpp:160-175 over the batch):
 // *d_status |= 4 if some class of some stripe lost two or more blocks.  The
 // caller zeroes *d_status first (stream-ordered).

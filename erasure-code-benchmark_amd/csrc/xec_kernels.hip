@@ -2764,6 +2764,289 @@ __global__ __launch_bounds__(T) void read_shards_kernel(uint8_t* out,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Shard-major degraded write and vectored read (xec_write_shards_device,
+// xec_readv_shards_device).
+//
+// The write is the list-tiled degraded write (write_list_kernel) with the list
+// checked on the device instead of the host: write_items_check_kernel leaves its
+// verdict in *status and write_shards_kernel is gated on it, so every item the
+// write sees is in range (c < S, i < k <= CAP), strictly ascending and servable.
+// Ownership is write_list_tile's; the two loss bits a host-checked list carries
+// per item are read here from the bitmap by the owner (scalar byte loads, as
+// write_class_kernel): the item's own byte and its class's parity byte.  Blocks
+// are addressed through the table,
+//   data block i of stripe c   : tab.v[i]     + c*dstride
+//   parity block j of stripe c : tab.v[k + j] + c*pstride
+// index and stripe offset wave-uniform and 64-bit.  write_shard_tile is
+// write_tile with those addresses -- a sibling, as xor_shard_members is
+// xor_members', so that write_tile and the batch write kernels stay instruction
+// for instruction what they were.  The lane helpers (write_plain, patch_fold,
+// patch_mix, patch_wave_add), the three modes, the store policies (new data
+// sc1, parity nt), the digest upkeep and the bounds argument are the batch
+// write's.  readv_shards_kernel is readv_dev_kernel with read_shards_kernel's
+// tile.  Emitted after everything above.
+// ---------------------------------------------------------------------------
+template <int U, bool NT, int T, bool DIG, uint32_t CAP, typename Src>
+__device__ __forceinline__ void write_shard_tile(const ShardTab<CAP>& tab, uint64_t doff,
+                                                 uint8_t* par, uint64_t* digests, int mode,
+                                                 uint64_t c, uint32_t j, uint32_t x,
+                                                 const WriteLane& w, const Geometry& g, Src src) {
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  uint64_t* row = digests + c * (g.k + g.m);
+  if (mode == kWriteDataOnly) {
+    src.each([&](uint32_t i, const uint8_t* fr) {
+      const uint64_t d = write_plain<U, NT, T, DIG>(tab.v[i] + doff, fr, w);
+      if constexpr (DIG) patch_wave_add(row + i, d);
+    });
+    return;
+  }
+  u32x4 acc[U];
+  uint64_t psum = 0;
+  if (mode == kWriteDelta) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (w.off + u * kStep < w.end) acc[u] = ld16<NT>(par + w.off + u * kStep);
+    if constexpr (DIG) psum = 0 - patch_mix<U, T>(acc, w.off, w.end, w.z);
+    src.each([&](uint32_t i, const uint8_t* fr) {
+      const uint64_t d = patch_fold<U, NT, T, DIG>(acc, tab.v[i] + doff, fr, w.off, w.end, w.z);
+      if constexpr (DIG) patch_wave_add(row + i, d);
+    });
+  } else {
+    // rebuild: every member has a source; acc becomes the new parity
+    const uint32_t nm = (uint32_t)g.nm, m = (uint32_t)g.m;
+    u32x4 oldx[U];  // DIG: XOR of the old bytes of every member but x
+    uint64_t dx = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      acc[u] = u32x4{0u, 0u, 0u, 0u};
+      oldx[u] = u32x4{0u, 0u, 0u, 0u};
+    }
+    // member block i with its bytes v loaded from `written ? new : data`
+    auto absorb = [&](uint32_t i, bool written, const u32x4(&v)[U]) {
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) acc[u] ^= v[u];
+      if (!written) {
+        if constexpr (DIG) {
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+            if (w.off + u * kStep < w.end) oldx[u] ^= v[u];
+        }
+        return;
+      }
+      if (i == x) {  // the lost member: its new bytes went into the parity only
+        if constexpr (DIG) dx = patch_mix<U, T>(v, w.off, w.end, w.z);
+        return;
+      }
+      uint8_t* block = tab.v[i] + doff;
+      if constexpr (DIG) {
+        u32x4 o[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (w.off + u * kStep < w.end) {
+            o[u] = ld16<NT>(block + w.off + u * kStep);
+            oldx[u] ^= o[u];
+          }
+        patch_wave_add(row + i, patch_mix<U, T>(v, w.off, w.end, w.z) -
+                                    patch_mix<U, T>(o, w.off, w.end, w.z));
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end)
+          st16_block<NT, kPatchDataStoreAux>(block, w.off + u * kStep, v[u]);
+    };
+    uint32_t r = 0;
+    // 8 members' loads in flight per granule, and not with DIG: as write_tile
+    for (; !DIG && r + 8 <= nm; r += 8) {
+      const uint8_t* from[8];
+      bool wr[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const uint32_t i = j + (r + q) * m;
+        const uint8_t* fr = nullptr;
+        wr[q] = src.written(r + q, fr);
+        from[q] = wr[q] ? fr : tab.v[i] + doff + w.off;
+      }
+      u32x4 v[8][U];
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+          if (w.off + u * kStep < w.end) v[q][u] = ld16<NT>(from[q] + u * kStep);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) absorb(j + (r + q) * m, wr[q], v[q]);
+    }
+    for (; r < nm; ++r) {
+      const uint32_t i = j + r * m;
+      const uint8_t* fr = nullptr;
+      const bool wr = src.written(r, fr);
+      const uint8_t* from = wr ? fr : tab.v[i] + doff + w.off;
+      u32x4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) v[u] = ld16<NT>(from + u * kStep);
+      absorb(i, wr, v);
+    }
+    if constexpr (DIG) {
+      u32x4 pold[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (w.off + u * kStep < w.end) {
+          pold[u] = ld16<NT>(par + w.off + u * kStep);
+          oldx[u] ^= pold[u];  // what block x virtually held
+        }
+      psum = 0 - patch_mix<U, T>(pold, w.off, w.end, w.z);
+      patch_wave_add(row + x, dx - patch_mix<U, T>(oldx, w.off, w.end, w.z));
+    }
+  }
+  if constexpr (DIG) psum += patch_mix<U, T>(acc, w.off, w.end, w.z);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (w.off + u * kStep < w.end)
+      st16_block<NT, kPatchParityStoreAux>(par, w.off + u * kStep, acc[u]);
+  if constexpr (DIG) patch_wave_add(row + g.k + j, psum);
+}
+
+// (list position, chunk of the range) tiles over a device list and bitmap,
+// gated on write_items_check_kernel's verdict.  The first item of a (stripe,
+// class) owns the class; an item of another stripe ends the walk back, so the
+// same class index in the previous stripe is not an earlier owner.
+template <int U, bool NT, int T, bool DIG, uint32_t CAP>
+__global__ __launch_bounds__(T) void write_shards_kernel(const uint8_t* __restrict__ fresh,
+                                                         const uint32_t* __restrict__ items,
+                                                         const uint8_t* __restrict__ bitmap,
+                                                         uint64_t* digests, ReadRange rr,
+                                                         Geometry g, uint64_t dstride,
+                                                         uint64_t pstride, ShardTab<CAP> tab) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  const uint64_t n = g.total_tiles / g.tiles_per_block;
+  const uint32_t m = (uint32_t)g.m;
+  auto at = [&](uint64_t q) { return *(const_u32_as4)(items + q); };
+  for (uint64_t t0 = blockIdx.x; t0 < g.total_tiles; t0 += gridDim.x) {
+    const uint64_t t = g.total_tiles - 1 - t0;  // from the end of the list, as write_list_kernel
+    const uint64_t e = t / g.tiles_per_block, chunk = t % g.tiles_per_block;
+    const uint32_t item = at(e);
+    const uint32_t c = item >> 8, j = (item & 0xFFu) % m;
+    bool owner = true;
+    for (uint64_t q = e; q > 0;) {
+      const uint32_t prev = at(--q);
+      if ((prev >> 8) != c) break;
+      if ((prev & 0xFFu) % m == j) { owner = false; break; }  // an earlier item's tile handles it
+    }
+    if (!owner) continue;
+    const uint64_t brow = reinterpret_cast<uint64_t>(bitmap) + (uint64_t)c * (g.k + g.m);
+    bool lost = false, plost = false;
+    uint32_t x = 0;
+    if (bitmap != nullptr) {
+      for (uint64_t q = e; q < n; ++q) {
+        const uint32_t it = at(q);
+        if ((it >> 8) != c) break;
+        const uint32_t i = it & 0xFFu;
+        if (i % m != j) continue;
+        if (sbyte(brow + i) == 0) {
+          lost = true;
+          x = i;
+        }
+      }
+      plost = sbyte(brow + g.k + j) == 0;
+    }
+    const int mode = plost ? kWriteDataOnly : lost ? kWriteRebuild : kWriteDelta;
+    WriteLane w;
+    w.off = rr.offset + (chunk * (uint64_t)(T * U) + threadIdx.x) * 16;
+    w.end = rr.offset + rr.len;
+    w.z = (w.off / 8 + 1) * kSplitmixGolden;
+    // item t's new bytes of this lane's first granule: fresh + t*len + its distance from `offset`
+    write_shard_tile<U, NT, T, DIG>(tab, (uint64_t)c * dstride,
+                                    tab.v[g.k + j] + (uint64_t)c * pstride, digests, mode, c, j, x,
+                                    w, g,
+                                    ListWritten<decltype(at)>{at, e, n, c, j, m,
+                                                              fresh + (w.off - rr.offset), rr.len});
+  }
+}
+
+// One thread per item: *status = max(*status, verdict) over the items, verdict
+// 3 for c >= S, i >= k or an item not above its predecessor (raw words, so
+// disorder and repeats alike), 4 for a lost block with another block of its
+// class lost too.  An item out of range never indexes the bitmap; bitmap ==
+// nullptr means everything is present and leaves the order rule.
+__global__ __launch_bounds__(256) void write_items_check_kernel(const uint8_t* __restrict__ bitmap,
+                                                               const uint32_t* __restrict__ items,
+                                                               uint64_t n, Geometry g,
+                                                               int32_t* status) {
+  const uint64_t row = g.k + g.m;
+  for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < n;
+       t += (uint64_t)gridDim.x * 256) {
+    const uint32_t item = items[t];
+    const uint64_t c = item >> 8, i = item & 0xFFu;
+    const bool in_range = c < g.S && i < g.k;
+    int32_t verdict = !in_range || (t > 0 && items[t - 1] >= item) ? 3 : 0;
+    if (in_range && bitmap != nullptr && bitmap[c * row + i] == 0) {
+      const uint8_t* r = bitmap + c * row;
+      const uint64_t j = i % g.m;
+      uint32_t others = r[g.k + j] == 0;
+      for (uint64_t l = j; l < g.k; l += g.m) others += l != i && r[l] == 0;
+      if (others != 0) verdict = 4;
+    }
+    if (verdict != 0) atomicMax(status, verdict);
+  }
+}
+
+// readv_dev_kernel over a shard table: gated on the verdict of readv_check_kernel
+// and readv_scan_kernel, the schedule in `work` as there, the tile
+// read_shards_kernel's with the entry's own range and slot.
+template <int NM, int U, bool NT, int T, uint32_t CAP>
+__global__ __launch_bounds__(T) void readv_shards_kernel(uint8_t* out,
+                                                         const uint32_t* __restrict__ iov,
+                                                         const uint8_t* __restrict__ bitmap,
+                                                         const uint32_t* __restrict__ work,
+                                                         uint32_t n, Geometry g, uint64_t dstride,
+                                                         uint64_t pstride, ShardTab<CAP> tab) {
+  if (*(const_i32_as4)g.gate != 0) return;
+  constexpr uint64_t kStep = (uint64_t)T * 16;
+  const uint32_t nm = NM > 0 ? (uint32_t)NM : (uint32_t)g.nm;
+  const uint32_t m = (uint32_t)g.m, k = (uint32_t)g.k;
+  const uint32_t* tiles = work + 2 * ((uint64_t)n + 1);
+  auto tile = [&](uint32_t x) { return *(const_u32_as4)(tiles + x); };
+  const uint32_t total = tile(n);
+  for (uint64_t t0 = blockIdx.x; t0 < total; t0 += gridDim.x) {
+    const uint32_t t = total - 1 - (uint32_t)t0;
+    const uint32_t e = readv_find(tile, n, t);
+    const uint32_t* ent = iov + 3 * (uint64_t)e;
+    const uint32_t item = *(const_u32_as4)ent;
+    const ReadRange rr{*(const_u32_as4)(ent + 1), *(const_u32_as4)(ent + 2)};
+    const uint64_t start = (uint64_t) * (const_u32_as4)(work + 2 * (uint64_t)e + 1) << 32 |
+                           *(const_u32_as4)(work + 2 * (uint64_t)e);
+    const uint64_t c = item >> 8;
+    const uint32_t i = item & 0xFFu;
+    const bool lost = bitmap != nullptr &&
+                      sbyte(reinterpret_cast<uint64_t>(bitmap) + c * (g.k + g.m) + i) == 0;
+    const uint64_t end = rr.offset + rr.len;
+    const uint32_t len = (uint32_t)rr.len;
+    const uint64_t off = rr.offset + ((uint64_t)(t - tile(e)) * (uint64_t)(T * U) + threadIdx.x) * 16;
+    uint8_t* slot = out + start;
+    auto store = [&](uint64_t o, u32x4 v) { st16_slot<NT>(slot, len, o - rr.offset, v); };
+    if (!lost) {
+      const uint8_t* blk = tab.v[i] + c * (i < k ? dstride : pstride);
+      u32x4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (off + u * kStep < end) v[u] = ld16<NT>(blk + off + u * kStep);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (off + u * kStep < end) store(off + u * kStep, v[u]);
+      continue;
+    }
+    const uint32_t j = i < k ? i % m : i - k;  // the entry's class
+    if (i < k)  // a data block: the other members and the class parity, as decode
+      xor_shard_members_to<NM, U, NT, T>(tab, j, g.m, c * dstride, tab.v[g.k + j] + c * pstride,
+                                         (int)(i / m), off, end, nm, store);
+    else  // a parity block: every data member, as encode
+      xor_shard_members_to<NM, U, NT, T>(tab, j, g.m, c * dstride, nullptr, -1, off, end, nm,
+                                         store);
+  }
+}
+
 namespace {
 
 // The k + m of h_shards in a ShardTab<CAP>, the rest null (never indexed).
@@ -2885,6 +3168,64 @@ hipError_t launch_read_shards(const void* const* h_shards, uint64_t dstride, uin
     constexpr uint32_t CAP = decltype(cap)::value;
     return launch_codec(read_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s, out,
                         d_items, d_bitmap, rr, g, dstride, pstride,
+                        shard_tab<CAP>(h_shards, g.k + g.m));
+  });
+}
+
+// launch_write's list tiles over a shard table, list and bitmap on the device
+// (g.gate must be set: launch_write_items_check's verdict).
+hipError_t launch_write_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                               const void* d_new, const uint32_t* d_items,
+                               const uint8_t* d_bitmap, uint64_t* d_digests,
+                               const Geometry& g_class, const LaunchShape& ls, uint64_t offset,
+                               uint64_t len, uint64_t n_items, hipStream_t s) {
+  if (n_items == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g_class) || d_new == nullptr || d_items == nullptr || len == 0 ||
+      offset % 16 != 0 || len % 16 != 0 || offset + len > g_class.bs || g_class.gate == nullptr)
+    return hipErrorInvalidValue;
+  const Geometry g = range_geometry(g_class, ls, len, n_items);
+  const ReadRange rr{offset, len};
+  const uint8_t* f = static_cast<const uint8_t*>(d_new);
+  const uint32_t grid = grid_for(g.total_tiles, ls.max_grid, ls.threads);
+  return with_shape(ls.unroll, ls.nt, ls.threads, [&](auto sh) {
+    constexpr int U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    return with_bool(d_digests != nullptr, [&](auto dig) {
+      constexpr bool DIG = decltype(dig)::value;
+      return with_shard_capacity(g.k + g.m, [&](auto cap) {
+        constexpr uint32_t CAP = decltype(cap)::value;
+        return launch_codec(write_shards_kernel<U, NT, T, DIG, CAP>, grid, T, ls.lds_bytes, s, f,
+                            d_items, d_bitmap, d_digests, rr, g, dstride, pstride,
+                            shard_tab<CAP>(h_shards, g.k + g.m));
+      });
+    });
+  });
+}
+
+hipError_t launch_write_items_check(const uint8_t* d_bitmap, const uint32_t* d_items, uint64_t n,
+                                    const Geometry& g, int32_t* d_status, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  return launch(write_items_check_kernel, grid_for((n + 255) / 256, 8192, 256), 256, 0, s,
+                d_bitmap, d_items, n, g, d_status);
+}
+
+// launch_readv with kReadDevTiles over a shard table (g.gate must be set).
+hipError_t launch_readv_shards(const void* const* h_shards, uint64_t dstride, uint64_t pstride,
+                               void* d_out, const Geometry& g, const LaunchShape& ls, uint64_t n,
+                               uint64_t tiles, const uint32_t* d_iov, const uint8_t* d_bitmap,
+                               const uint32_t* d_work, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!shard_launch_ok(h_shards, g) || d_out == nullptr || d_iov == nullptr ||
+      d_work == nullptr || n > 0xFFFFFFFFull || tiles > 0xFFFFFFFFull || g.gate == nullptr)
+    return hipErrorInvalidValue;
+  uint8_t* out = static_cast<uint8_t*>(d_out);
+  const uint32_t grid = grid_for(tiles, ls.max_grid, ls.threads);
+  return with_shard_shape(g, ls, [&](auto sh, auto cap) {
+    constexpr int NM = decltype(sh)::NM, U = decltype(sh)::U, T = decltype(sh)::T;
+    constexpr bool NT = decltype(sh)::NT;
+    constexpr uint32_t CAP = decltype(cap)::value;
+    return launch_codec(readv_shards_kernel<NM, U, NT, T, CAP>, grid, T, ls.lds_bytes, s, out,
+                        d_iov, d_bitmap, d_work, (uint32_t)n, g, dstride, pstride,
                         shard_tab<CAP>(h_shards, g.k + g.m));
   });
 }

@@ -23,7 +23,8 @@ from .codec import (DECODE_KERNELS, Pipeline, build_info, check_args, check_bitm
                     write_tiling_used,
                     check_shards, encode_shards, repair_shards_device, shard_table,
                     shards_arg_capacity_used, verify_shards,
-                    digest_shards, locate_shards, read_shards_device)
+                    digest_shards, locate_shards, read_shards_device,
+                    readv_shards_device, write_shards_device)
 from .partition import stripe_range
 
 __all__ = [
@@ -46,4 +47,5 @@ __all__ = [
     "check_shards", "encode_shards", "repair_shards_device", "shard_table",
     "shards_arg_capacity_used", "verify_shards",
     "digest_shards", "locate_shards", "read_shards_device",
+    "readv_shards_device", "write_shards_device",
 ]

@@ -43,6 +43,7 @@ EXPORTED = (
     "xec_check_shards", "xec_encode_shards", "xec_repair_shards_device", "xec_verify_shards",
     "xec_shards_arg_capacity_used",
     "xec_digest_shards", "xec_locate_shards", "xec_read_shards_device",
+    "xec_write_shards_device", "xec_readv_shards_device",
 )
 
 
@@ -163,6 +164,10 @@ def lib() -> ctypes.CDLL:
         "xec_locate_shards": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, vp, vp, vp, sz, vp], st),
         "xec_read_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp],
                                    st),
+        "xec_write_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, sz, sz, vp, vp, vp,
+                                     vp], st),
+        "xec_readv_shards_device": ([vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, vp, sz, vp, sz, vp,
+                                     vp], st),
         "xec_set_rotation": ([ctypes.c_int], st),
         "xec_get_tuning": ([ctypes.POINTER(Tuning)], st),
         "xec_set_tuning": ([ctypes.POINTER(Tuning)], st),

@@ -204,6 +204,41 @@ def read_shards_device(shards, data_stride: int, parity_stride: int, S: int, bs:
                                                _ptr(d_status), _stream(stream)))
 
 
+def write_shards_device(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int,
+                        m: int, d_bitmap, d_items, n_items: int, offset: int, length: int, d_new,
+                        d_digests, d_status, stream=None) -> Status:
+    """xec_write_shards_device -- xec_write over shards with the list on the
+    device: the blocks the ascending device items c << 8 | i (i < k) name take
+    bytes [offset, offset + length) from d_new (item t at d_new + t*length) and
+    parity follows, in the delta, data-only or rebuild-write mode d_bitmap (byte
+    0 = lost; None = all present, the ranged update) asks for; d_digests (uint64
+    device tensor or None) is kept current; the verdict (0, 3 or 4) lands in
+    d_status.  Capturable."""
+    return Status(lib().xec_write_shards_device(shard_table(shards), data_stride, parity_stride,
+                                                S, bs, k, m,
+                                                _ptr(d_bitmap) if d_bitmap is not None else None,
+                                                _ptr(d_items) if d_items is not None else None,
+                                                n_items, offset, length,
+                                                _ptr(d_new) if d_new is not None else None,
+                                                _ptr(d_digests) if d_digests is not None else None,
+                                                _ptr(d_status), _stream(stream)))
+
+
+def readv_shards_device(shards, data_stride: int, parity_stride: int, S: int, bs: int, k: int,
+                        m: int, d_bitmap, d_iov, n_items: int, d_out, out_bytes: int, d_work,
+                        work_bytes: int, d_status, stream=None) -> Status:
+    """xec_readv_shards_device -- xec_readv_device over shards: each device entry
+    (item, offset, len) delivers its range, packed in list order, to d_out;
+    d_work of readv_device_work_bytes(n_items) device bytes; the verdict (0, 1,
+    3 or 4) lands in d_status.  Capturable."""
+    return Status(lib().xec_readv_shards_device(shard_table(shards), data_stride, parity_stride,
+                                                S, bs, k, m,
+                                                _ptr(d_bitmap) if d_bitmap is not None else None,
+                                                _ptr(d_iov) if d_iov is not None else None,
+                                                n_items, _ptr(d_out), out_bytes, _ptr(d_work),
+                                                work_bytes, _ptr(d_status), _stream(stream)))
+
+
 def shards_arg_capacity_used() -> int:
     """xec_shards_arg_capacity_used: the pointer capacity (64 or 256) of this
     thread's last shard call's kernel arguments; 0 if it launched nothing."""

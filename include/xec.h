@@ -258,9 +258,14 @@ xec_status xec_verify(const void* d_data, const void* d_parity, size_t S, size_t
  * and h_shards is read before the call returns -- there is no other host
  * work, so every call is capturable, and a replay uses the pointers of the
  * capture.  Shard forms exist for encode, the device-bitmap repair, the
- * scrub, digest, locate and the device-resident degraded read; readv, write and
- * update (xec_update, xec_update_range) are batch-only so far, and so are the
- * host-list forms (xec_read, xec_repair, xec_decode).  Every table entry must be
+ * scrub, digest, locate, the device-resident degraded read and vectored read,
+ * and the degraded write (xec_write_shards_device, which with a NULL bitmap is
+ * the ranged update and with the whole block as its range the update): the
+ * device-resident surface is complete.  Out of scope and batch-only: the
+ * host-list forms (xec_read, xec_readv, xec_write, xec_update, xec_update_range,
+ * xec_repair, xec_decode), a mask / shadow form of the write or the update, a
+ * range per written item (a writev), and residency sweeps on this layout.
+ * Every table entry must be
  * a valid shard in every call, a dead shard with no memory behind it included:
  * a lost block is never read, but its address must still pass xec_check_shards.
  * When to use which (tools/shards_bench.py on one MI355X, configs 2, 3 and 4 --
@@ -458,10 +463,83 @@ xec_status xec_read_shards_device(const void* const* h_shards, size_t data_strid
                                   size_t n_items, size_t offset, size_t len, void* d_out,
                                   int32_t* d_status, hipStream_t stream);
 
+/* xec_write over shards, device-resident: a store with a shard down takes a
+ * small write in place.  The semantics are xec_write's, word for word, over the
+ * table: items c << 8 | i with i < k, strictly ascending; one range
+ * [offset, offset + len) per call, multiples of 16; item t's new bytes at
+ * d_new + t*len; every (stripe, class) with an item runs in the delta, data-only
+ * or rebuild-write mode; servability is xec_read's rule, all-or-nothing over the
+ * items; the digest upkeep in all three modes (d_digests may be NULL) is exactly
+ * what xec_write describes; a lost block is never read and never written, and
+ * bytes of a shard between its blocks are never touched.  d_bitmap == NULL
+ * means everything is present: the call is then xec_update_range over shards,
+ * and with offset = 0, len = bs xec_update -- one call covers update, ranged
+ * update and degraded write, there are no separate update entry points.  It
+ * takes what xec_read_shards_device takes on the read side, a device list and
+ * the bytes packed in list order, not xec_write_device's mask over a shadow of
+ * the whole data range: a shard store has no second copy of every shard.
+ * Through a table aliased into a batch it leaves exactly xec_write's bytes and
+ * digest slots, and is the capturable list form of the batch write.
+ * Checks, all on the host before anything is queued, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. d_status NULL or not 4-byte aligned -> XEC_INVALID_ALIGNMENT;
+ *  4. n_items == 0 or S == 0 -> XEC_SUCCESS with only *d_status = 0 queued;
+ *  5. k + m > 256 or S > 2^24 -> XEC_INVALID_SIZE;
+ *  6. the range, step 5 of xec_update_range;
+ *  7. d_new or d_items NULL -> XEC_INVALID_SIZE;
+ *  8. d_new not 16-byte aligned, d_items not 4-byte aligned, or d_digests not
+ *     NULL and not 8-byte aligned -> XEC_INVALID_ALIGNMENT;
+ *  9. n_items * len not representable -> XEC_INVALID_SIZE (the tile count is at
+ *     most n_items * len / 16, so it fits whenever that does);
+ * 10. steps 3 to 7 of xec_check_shards;
+ * 11. d_new's n_items*len bytes or d_digests' 8*S*(k+m) bytes meet the hull of
+ *     any shard (the rule of xec_read_shards_device step 5), or each other ->
+ *     XEC_INVALID_SIZE; ranges that only touch are allowed.
+ * A rejected call queues nothing.  Enqueues on `stream`, with no host work
+ * beyond reading h_shards, so the call is capturable (one memset node) and a
+ * replay applies whatever d_items, d_bitmap and d_new hold then: *d_status = 0
+ * (a memset, as xec_read_shards_device); a check kernel, one thread per item,
+ * that leaves *d_status at the MAXIMUM over the items of 0 (acceptable), 3
+ * (c >= S, i >= k, or t > 0 and items[t-1] >= items[t], compared on the raw
+ * words: disorder and repeats) and 4 (the block is lost and another block of
+ * its class is lost too) -- an item with c >= S or i >= k never indexes the
+ * bitmap, and the kernel runs with d_bitmap NULL as well, for the order rule;
+ * then the write kernel over (list position, chunk of the range) tiles, which
+ * does nothing if *d_status != 0.  NOTE the difference from the host form: in
+ * xec_write a broken item rule (XEC_INVALID_COUNTS, 3) outranks an unservable
+ * item (4) wherever they stand; here the verdict is the maximum, so a list with
+ * both reports 4, as xec_read_device's does.  The first item of a (stripe,
+ * class) owns that class's parity granules and reads its mode from the bitmap:
+ * the item's own byte and the byte of its class's parity block.  New data is
+ * stored sc1, parity nt.  There is no limit on n_items.  Of xec_set_launch all
+ * four arguments apply, xec_set_rotation does not; residency is uncapped, as
+ * for xec_write, swept on the batch layout only.  xec_write_tiling_used is not
+ * affected, as xec_read_tiling_used is not by xec_read_shards_device.
+ * Measured against xec_write on the same items (tools/shards_bench.py, one
+ * MI355X, configs 2 / 3 / 4, kernel times, profiles/shards/write_readv_bench.json,
+ * DESIGN.md §3 *Shard layout*; the check kernel is not in these times): 4 KiB into
+ * each of min(S, 1,024) LOST blocks (rebuild-write) took 1.09 / 1.22 / 1.08 of
+ * xec_write's kernel aliased into the batch (9.6, 8.0 and 26 us there) and 1.14 /
+ * 1.26 / 1.19 on separate allocations; the same with the blocks present (delta)
+ * 1.17 / 1.03 / 1.16 and 1.09 / 1.02 / 1.16 on kernels of 4-5 us whose rounds
+ * spread up to 9 %; one whole lost block per stripe 1.03 / 1.00 / 1.00 and 1.03 /
+ * 1.10 / 1.03; one whole present block per stripe 1.06 / 1.02 / 1.03 and 1.06 /
+ * 1.10 / 0.99 (spreads 0.1-3 %). */
+xec_status xec_write_shards_device(const void* const* h_shards, size_t data_stride,
+                                   size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                   const uint8_t* d_bitmap, const uint32_t* d_items, size_t n_items,
+                                   size_t offset, size_t len, const void* d_new,
+                                   uint64_t* d_digests, int32_t* d_status, hipStream_t stream);
+
+/* xec_readv_shards_device, the vectored read over shards, stands with
+ * xec_readv_device below: it takes that call's xec_iov entries. */
+
 /* Diagnostics: how many pointers the kernel-argument table of the calling
  * thread's most recent shard call (xec_encode_shards, xec_repair_shards_device,
- * xec_verify_shards, xec_digest_shards, xec_locate_shards or
- * xec_read_shards_device) could hold -- 64 or 256, the smaller capacity that holds
+ * xec_verify_shards, xec_digest_shards, xec_locate_shards,
+ * xec_read_shards_device, xec_write_shards_device or
+ * xec_readv_shards_device) could hold -- 64 or 256, the smaller capacity that holds
  * k + m; 0 when that call launched nothing (an error, S == 0, or no items). */
 int xec_shards_arg_capacity_used(void);
 
@@ -823,6 +901,45 @@ xec_status xec_readv_device(const void* d_data, const void* d_parity, size_t S, 
  * the totals), 0 for n_items == 0. */
 size_t xec_readv_device_work_bytes(size_t n_items);
 
+/* xec_readv_device over shards: serve a read queue whose ranges differ from a
+ * store with a shard down.  d_bitmap (NULL = everything present), d_iov (item,
+ * offset, len per entry; present and lost blocks, data and parity, repeats, any
+ * order), d_out and out_bytes, d_work (xec_readv_device_work_bytes(n_items)
+ * bytes: the size serves both layouts), the verdicts 0 / 1 / 3 / 4 left as a
+ * maximum in *d_status and the all-or-nothing behaviour over the entries are
+ * xec_readv_device's, and so is what is queued: *d_status = 0 (a memset), the
+ * same check and scan kernels -- neither touches a block -- then a read kernel
+ * that does nothing if *d_status != 0, its grid fixed from the same bound.  A
+ * lost block is never read and nothing but d_out, d_work and *d_status is
+ * written.  Checks, in this order:
+ *  1. XEC_NOT_INITIALIZED;
+ *  2. step 1 of xec_check_shards;
+ *  3. xec_readv_device's own checks in its order, from d_status up to the
+ *     alignments of d_out, d_iov and d_work;
+ *  4. steps 3 to 7 of xec_check_shards;
+ *  5. d_out's out_bytes meet the hull of any shard -> XEC_INVALID_SIZE (the
+ *     rule of xec_read_shards_device step 5: a d_out in a gap between two
+ *     blocks of one shard is refused, ranges that only touch are allowed);
+ *  6. n_items * ceil(bs / 1024) >= 2^32 -> XEC_INVALID_SIZE.
+ * A rejected call queues nothing.  Bytes of a shard between its blocks are
+ * never read; aliased into a batch it delivers exactly xec_readv_device's
+ * bytes.  Capturable (one memset node).  xec_set_launch as xec_readv_device, no
+ * column rotation, residency by xec_read_device's table, swept on the batch
+ * layout only.  xec_readv_tiling_used is not affected.  Measured against
+ * xec_readv_device on the same entries (same tool, file and configs; the read
+ * kernel alone): 4 KiB of each of min(S, 1,024) lost blocks took 1.06 / 0.95 /
+ * 1.10 aliased (the batch kernel's rounds spread 12 % at config 3) and 1.08 /
+ * 1.09 / 1.18 on separate allocations; of present blocks 1.02 / 1.05 / 1.07 and
+ * 1.06 / 1.03 / 1.05; one whole lost block per stripe 1.02 / 1.00 / 1.24 and
+ * 1.05 / 1.03 / 1.21 -- config 4 is the 32-member reconstruction whose member
+ * addresses are scalar loads, as for xec_read_shards_device; one whole present
+ * block per stripe 1.00 / 1.09 / 1.00 and 0.98 / 1.12 / 1.00. */
+xec_status xec_readv_shards_device(const void* const* h_shards, size_t data_stride,
+                                   size_t parity_stride, size_t S, size_t bs, size_t k, size_t m,
+                                   const uint8_t* d_bitmap, const xec_iov* d_iov, size_t n_items,
+                                   void* d_out, size_t out_bytes, void* d_work, size_t work_bytes,
+                                   int32_t* d_status, hipStream_t stream);
+
 /* Host-only plan check xec_readv runs over its entries (no GPU and no xec_init
  * needed): steps 7, 9 and 10 of xec_readv in that order.  k, m invalid as in
  * xec_check_args, or h_iov NULL with n_items > 0 -> XEC_INVALID_COUNTS, as
@@ -1176,7 +1293,9 @@ xec_status xec_set_validate_kernel(int mode);
  * 1..2^20 = that many chunks per stripe.  XEC_INVALID_SIZE outside -1..2^20.
  * It does not apply to xec_read / xec_read_device, xec_readv / xec_readv_device,
  * xec_update / xec_update_device, xec_update_range / xec_update_range_device
- * and xec_write / xec_write_device: their tiles walk the chunks of each item's
+ * and xec_write / xec_write_device, nor to xec_read_shards_device,
+ * xec_readv_shards_device and xec_write_shards_device: their tiles walk the
+ * chunks of each item's
  * byte range, not a column of every stripe.  (xec_update and xec_update_device
  * applied an explicit rotation while they had kernels of their own; the
  * automatic setting was none for them, so only a caller that set one sees the
@@ -1224,7 +1343,8 @@ int xec_decode_arg_capacity_used(void);
  * xec_digest, xec_locate, xec_read, xec_read_device, xec_readv, xec_readv_device, xec_update_range,
  * xec_update_range_device, xec_encode_shards, xec_repair_shards_device,
  * xec_verify_shards, xec_digest_shards, xec_locate_shards,
- * xec_read_shards_device, xec_write or xec_write_device call
+ * xec_read_shards_device, xec_write_shards_device, xec_readv_shards_device,
+ * xec_write or xec_write_device call
  * launches its encode / decode / repair / verify / update / digest / read / write kernel with hipExtLaunchKernel and these two
  * events (either may be NULL), which the runtime records from that kernel's
  * own dispatch: hipEventElapsedTime(start, stop) is the kernel's execution

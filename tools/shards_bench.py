@@ -5,10 +5,13 @@ For configs 2, 3 and 4 of BASELINE.json each operation -- encode, the scrub, the
 device repair with every parity block lost and with one data block lost per
 stripe; the digest of every block, the locate over the flags of one class in
 64, the degraded read of one whole lost block per stripe and of 4 KiB from each
-of min(S, 1024) lost blocks -- runs in four placements of the same bytes:
+of min(S, 1024) lost blocks; the degraded write and the vectored read of 4 KiB
+of each of min(S, 1024) blocks and of one whole block per stripe, those blocks
+lost and present -- runs in four placements of the same bytes:
 
   batch    the existing batch call (xec_encode, xec_verify, xec_repair_device,
-           xec_digest, xec_locate, xec_read_device);
+           xec_digest, xec_locate, xec_read_device; xec_write and
+           xec_readv_device on the same items);
   alias    the shard call on pointers aliased into that same batch: the same
            addresses, so the difference is the cost of table addressing alone;
   sep      k + m separate allocations, stride = bs;
@@ -16,8 +19,10 @@ of min(S, 1024) lost blocks -- runs in four placements of the same bytes:
 
 `sep` puts the members of a class S*bs apart, a large power of two -- the access
 pattern column rotation exists for -- so it also runs with rotation off
-(sep_rot-1) and on (sep_rot3); rotation applies to none of digest, locate and
-read, which run in the four placements only.
+(sep_rot-1) and on (sep_rot3); rotation applies to none of digest, locate, read,
+write and readv, which run in the four placements only.  The writes come last:
+they change the store (every placement takes the same new bytes, and the lost
+blocks are repaired before the placements are compared).
 
 Kernel times come from each call's own dispatch (xec_set_kernel_events).  The
 placements of an operation are interleaved round by round; a figure is the
@@ -54,8 +59,12 @@ sys.path.insert(0, str(ROOT / "erasure-code-benchmark_amd"))
 CONFIGS = {"cfg2": (8, 1, 1 << 16, 1024), "cfg3": (16, 1, 1 << 20, 256),
            "cfg4": (32, 1, 4096, 65536)}  # k, m, bs, S (bench.py WORKLOADS)
 PAD = 4096
+# write / readv legs: <call>_<4k | block>_<lost | present>, the items the lost data block of
+# each stripe (bitmap given) or the same blocks with everything present (no bitmap)
+RW_OPS = [f"{call}_{size}_{state}" for call in ("readv", "write") for size in ("4k", "block")
+          for state in ("lost", "present")]
 OPS = ["encode", "verify", "repair_parity", "repair_data", "digest", "locate_flags", "read_block",
-       "read_4k"]
+       "read_4k"] + RW_OPS
 NO_ROTATION = OPS[4:]  # xec_set_rotation applies to none of these
 READ_4K_ITEMS, READ_4K_LEN = 1024, 4096
 
@@ -105,9 +114,56 @@ class Placement:
         self.work = torch.empty(n, dtype=torch.int64, device="cuda")
         self.bitmap = torch.empty(n, dtype=torch.uint8, device="cuda")
         self.out = torch.empty(S * bs, dtype=torch.uint8, device="cuda")
+        self.rwork = torch.empty(xec.readv_device_work_bytes(S) // 8, dtype=torch.int64,
+                                 device="cuda")
+        self.scratch = torch.empty(xec.write_scratch_bytes(S) // 4 + 1, dtype=torch.int32,
+                                   device="cuda")
+
+    def rw_items(self, op):
+        """(items, bytes of each) of a write / readv leg."""
+        return (self.S, self.bs) if "_block_" in op else (min(self.S, READ_4K_ITEMS), READ_4K_LEN)
+
+    def data_blocks(self):
+        """The data blocks of the batch, or of separate allocations, as (S, k, bs)."""
+        S, k, bs = self.S, self.k, self.bs
+        if self.batch is not None:
+            return self.batch[0].view(S, k, bs)
+        return self.torch.stack([t.view(S, self.ds)[:, :bs] for t in self.keep[:k]], dim=1)
+
+    def call_rw(self, op, bm, s):
+        x, a = self.xec, (self.S, self.bs, self.k, self.m)
+        call, _, state = op.split("_")
+        n, length = self.rw_items(op)
+        d_bm = bm["repair_data"] if state == "lost" else None
+        if call == "readv":
+            iov, wb = bm["iov_" + op.split("_")[1]], 8 * self.rwork.numel()
+            if self.batch is not None:
+                d, p = self.batch
+                return x.readv_device(d, p, *a, d_bm, iov, n, self.out, n * length, self.rwork, wb,
+                                      self.status, s)
+            return x.readv_shards_device(self.table, self.ds, self.ps, *a, d_bm, iov, n, self.out,
+                                         n * length, self.rwork, wb, self.status, s)
+        if self.batch is not None:
+            d, p = self.batch
+            return x.write(d, p, bm["new"], *a, bm["h_repair_data"] if state == "lost" else None,
+                           bm["h_items"], n, 0, length, None, self.scratch,
+                           4 * self.scratch.numel(), s)
+        return x.write_shards_device(self.table, self.ds, self.ps, *a, d_bm, bm["items"], n, 0,
+                                     length, bm["new"], None, self.status, s)
+
+    def heal(self, bm, s):
+        """Put the lost data blocks back after a degraded write."""
+        x, a = self.xec, (self.S, self.bs, self.k, self.m)
+        if self.batch is not None:
+            return x.repair_device(*self.batch, *a, bm["repair_data"], self.status, s)
+        return x.repair_shards_device(self.table, self.ds, self.ps, *a, bm["repair_data"],
+                                      self.status, s)
 
     def result(self, op):
         """What the last `op` left, for the comparison with the batch call's."""
+        if op in RW_OPS:
+            n, length = self.rw_items(op)
+            return self.out[:n * length]
         if op == "digest":
             return self.digests
         if op == "locate_flags":
@@ -117,6 +173,8 @@ class Placement:
 
     def call_integrity(self, op, bm, s):
         x, a = self.xec, (self.S, self.bs, self.k, self.m)
+        if op in RW_OPS:
+            return self.call_rw(op, bm, s)
         if self.batch is not None:
             d, p = self.batch
             if op == "digest":
@@ -212,6 +270,18 @@ def run_config(xec, torch, name, shape, rounds, iters, lim, ops):
               "repair_data": torch.from_numpy(data.reshape(-1)).to("cuda"),
               "items": torch.from_numpy(items.view(np.int32)).to("cuda"),
               "flags64": torch.from_numpy(flags64).to("cuda"), "stored": stored}
+        if any(op in RW_OPS for op in ops):
+            # the same items (ascending: one per stripe) for the write and the vectored read;
+            # one range per entry so that the batch and the shard call serve the same queue
+            bm["h_items"], bm["h_repair_data"] = items, np.ascontiguousarray(data.reshape(-1))
+            for size, length in (("4k", READ_4K_LEN), ("block", bs)):
+                iov = np.zeros(S, dtype=xec.IOV)
+                iov["item"], iov["len"] = items, length
+                bm["iov_" + size] = torch.from_numpy(iov.view(np.uint8).reshape(-1).copy()).to("cuda")
+            new = torch.empty(S * bs, dtype=torch.uint8, device="cuda")
+            assert xec.fill_splitmix64(new, S, bs, 7321, s) == 0
+            bm["new"] = new
+        torch.cuda.synchronize()
         torch.cuda.synchronize()
     rows = []
     for op in ops:
@@ -222,17 +292,33 @@ def run_config(xec, torch, name, shape, rounds, iters, lim, ops):
                 with step(lim, f"{name} {op} round {r} {label(pl)}"):
                     per[label(pl)].append(pl.time_round(op, bm, iters, ev, s))
         med = {n: statistics.median(v) for n, v in per.items()}
-        row = {"config": name, "shape": list(shape), "op": op, "bytes": (k + m) * bs * S,
-               "placements": {}}
+        nbytes = (k + m) * bs * S
+        if op in RW_OPS:  # the bytes delivered or taken, not the batch's
+            nbytes = pls[0].rw_items(op)[0] * pls[0].rw_items(op)[1]
+        row = {"config": name, "shape": list(shape), "op": op, "bytes": nbytes, "placements": {}}
         for n, v in per.items():
             row["placements"][n] = {
                 "round_medians_us": [round(x, 2) for x in v], "median_us": round(med[n], 2),
                 "spread_pct": round(100 * (max(v) - min(v)) / med[n], 2),
                 "time_over_batch": round(med[n] / med["batch"], 4),
-                "GBps_of_batch_bytes": round((k + m) * bs * S / med[n] / 1e3, 1)}
+                "GBps_of_batch_bytes": round(nbytes / med[n] / 1e3, 1)}
         print(json.dumps(row), flush=True)
         rows.append(row)
-        if op in NO_ROTATION:
+        if op.startswith("write_"):
+            with step(lim, f"{name} {op}: repair, then every placement holds the batch's data"):
+                n, length = pls[0].rw_items(op)
+                for pl in pls[:4]:
+                    if op.endswith("_lost"):
+                        assert pl.heal(bm, s) == 0
+                    torch.cuda.synchronize()
+                    assert int(pl.status.item()) == 0, f"{name} {op} {pl.name}"
+                want = pls[0].data_blocks()
+                c = torch.arange(n, device="cuda")
+                i = bm["items"][:n].to(torch.int64) & 0xFF
+                assert torch.equal(want[c, i, :length], bm["new"][:n * length].view(n, length))
+                for pl in pls[2:4]:
+                    assert torch.equal(pl.data_blocks(), want), f"{name} {op} {pl.name}"
+        elif op in NO_ROTATION:
             with step(lim, f"{name} {op}: every placement left what the batch call left"):
                 torch.cuda.synchronize()
                 assert int(pls[0].status.item()) == 0 and int(pls[0].count.item()) == 0
